@@ -13,8 +13,14 @@ psnr,ssim,fsim,icid` adds the others).  Frames shard across ranks (frame f -> ra
 the [frames, n_metrics] table is gathered with ONE RCCL all_gather at the end of the timed
 region (configs[4]).  `value` = all ranks' pairs / max-over-ranks wall time.
 
-Extra keys: `roofline` (dominant kernel, HIP events per launch), `cpu_baseline` (the numpy oracle
-of the same function, rank 0, N=1 only), `extra` (MK / Xiao / IDT rates, informational).
+A plain run sets up, warms up, times the K steps and prints the line; `ms_per_step` is the wall time of one timed step.
+`--full` adds what takes runs of its own: `roofline` (dominant kernel, HIP events per launch), `roofline_cnn` / `value_cnn`
+(dcmcs3di forward), `cpu_baseline` (the numpy oracle of the same function, rank 0, N=1 only), `extra` (MK / Xiao / IDT / CNN
+rates, the configs[4] video stream; informational).  Without `--full` those keys are null / empty.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's frames) as .npy files: the first corrected frame
+whole, a fixed seeded sample of all corrected frames, and the per-frame metric records.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +51,23 @@ BASELINE_METRIC = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
 # arithmetic the headline path computes in, per Lab mode (ct_set_lab_mode)
 DTYPE = {"table": "f32 (float32 I/O; float32 difference forms in both sweeps, float64 only in the per-frame statistics records)",
          "exact": "f64 (float32 I/O, float64 arithmetic)"}
+DUMP_SAMPLE = 1 << 22                        # float32 elements of the seeded output sample (16.8 MB; + one whole frame, 24.9 MB)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(d, out, records, on_cpu):
+    """What the last timed step computed, as DIR/<name>.npy (float32 / float64, < 64 MB in all).  `out` [B, H, W, 3] float32
+    corrected frames, `records` [B, cols] float64 per-frame metric rows of that step.  The dry run computes no frames."""
+    os.makedirs(d, exist_ok=True)
+    files = {"frame_metrics": records.detach().cpu().numpy().astype(np.float64)}
+    if not on_cpu:
+        flat = out.reshape(-1)
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=min(DUMP_SAMPLE, flat.numel()), dtype=np.int64))
+        files["reinhard_out_frame0"] = out[0].cpu().numpy().astype(np.float32)
+        files["reinhard_out_sample"] = flat[torch.from_numpy(idx).to(out.device)].cpu().numpy().astype(np.float32)
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in files.items()}
 
 
 def synth_frames(frame_ids, device):
@@ -109,10 +132,15 @@ def main():
     ap.add_argument("--metrics", default="psnr", help="per-frame metrics inside the timed region: psnr[,ssim,fsim,icid] or none")
     ap.add_argument("--init-seconds", type=float, default=0.25, help="clock / code-object initialisation before the warm-up steps")
     ap.add_argument("--video", type=int, default=0, help="also stream this many 1080p frames from pinned host memory (configs[4]; 0 = the default "
-                    "1000 on single-GPU runs with the extras, off otherwise)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+                    "1000 on single-GPU --full runs with the extras, off otherwise)")
+    ap.add_argument("--full", action="store_true", help="also measure the rooflines, the other paths and sizes (extra, value_cnn), the video "
+                    "stream and the CPU baseline; a plain run times the headline steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra paths")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -214,12 +242,15 @@ def main():
         dt = float(tmax.item())
     pairs_total = B * K * world
     value = pairs_total / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:              # before anything below re-uses `out`
+        dumped = dump_outputs(args.dump_outputs, out, metrics[K - 1], on_cpu)
 
     # ---- per-kernel roofline: HIP events around each launch group on the launch stream ----------
     roof = None
     roof_cnn = None
     extra = {}
-    if rank == 0 and not on_cpu:
+    if args.full and rank == 0 and not on_cpu:
         # exact per-kernel durations: the library records HIP events on the launch stream right before / after
         # moments_kernel<float,true> and reinhard_apply_kernel<float,false> of the same fused call that `value` times
         n_prof = min(K, 50)
@@ -554,7 +585,7 @@ def main():
             del dm
 
     # configs[4] with the uploads inside the measurement: every rank takes part (frame f -> rank f % world)
-    n_video = args.video if args.video > 0 else (1000 if (world == 1 and not args.no_extra) else 0)
+    n_video = args.video if args.video > 0 else (1000 if (args.full and world == 1 and not args.no_extra) else 0)
     if n_video > 0 and not on_cpu:
         del tgt, ref, gt, out
         torch.cuda.empty_cache()
@@ -562,7 +593,7 @@ def main():
         if rank == 0:
             extra["video_stream"] = vid
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not on_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not on_cpu:
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -585,7 +616,8 @@ def main():
                        "pairs_per_step_per_gpu": B, "io_dtype": "float32", "height": H, "width": W,
                        "lab_arithmetic": ct_hip.lab_mode(), "metrics": names,
                        "sharding": "frame f -> rank f % world; one all_gather of the [frames, n_metrics] table"},
-            "roofline": roof, "roofline_cnn": roof_cnn, "cpu_baseline": cpu, "extra": extra,
+            "roofline": roof, "roofline_cnn": roof_cnn, "cpu_baseline": cpu, "extra": extra, "full": args.full,
+            **({"dump_outputs": {"dir": args.dump_outputs, "step": K - 1, "files": dumped}} if dumped is not None else {}),
         }
         print(json.dumps(line), flush=True)
     if world > 1:

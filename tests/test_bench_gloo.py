@@ -9,6 +9,8 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -55,3 +57,24 @@ def test_bench_world1_dry_run_and_flag_mismatch():
     env = dict(os.environ, CT_BENCH_DEVICE="cpu")
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE" in (p.stderr + p.stdout)      # --gpus must match the launcher's world size
+
+
+def test_bench_dry_run_dump_outputs_and_plain_line(tmp_path):
+    """--dump-outputs writes the last timed step's per-frame records (the dry run computes no frames); a plain run measures
+    nothing beyond the timed steps (no roofline, CPU baseline or extras), and --full is accepted."""
+    steps, pairs = 3, 2
+    d = tmp_path / "out"
+    env = dict(os.environ, CT_BENCH_DEVICE="cpu", OMP_NUM_THREADS="1")
+    base = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--pairs", str(pairs), "--init-seconds", "0"]
+    p = subprocess.run(base + ["--dump-outputs", str(d)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert j["steps"] == steps and j["full"] is False and j["ms_per_step"] > 0
+    assert j["roofline"] is None and j["roofline_cnn"] is None and j["cpu_baseline"] is None and j["extra"] == {}
+    assert j["dump_outputs"]["step"] == steps - 1 and set(j["dump_outputs"]["files"]) == {"frame_metrics"}
+    m = np.load(d / "frame_metrics.npy")
+    assert m.dtype == np.float64 and m.shape == (pairs, 2)
+    np.testing.assert_array_equal(m, np.array([[i + 0.001 * (steps - 1)] * 2 for i in range(pairs)]))     # the stub's last step
+    p = subprocess.run(base + ["--full", "--no-extra", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])["full"] is True

@@ -69,7 +69,7 @@ for sub in sorted(os.listdir(SRC)):
                 short = k.split("ct::")[-1].split("(")[0].replace("void ", "")
                 per[short].update(d)
 alg = 2 * 3 * 4 * H * W * pairs            # two float32 frames per pair, read or written once by each sweep
-out = {**STAMPS, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* in separate passes over `bench.py --steps 20 --warmup 5` "
+out = {**STAMPS, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* in separate passes over `bench.py --full --steps 20 --warmup 5` "
                  "(tools/gpu_profile_round.sh, tools/collect_profiles_round.py)",
        "pairs_per_step": pairs, "lab_mode": bench["config"].get("lab_arithmetic"),
        "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request -> read bytes = 2 x FETCH_SIZE x 1024; WRITE_SIZE x 1024 (MI355X_MICROARCH.md, HBM)",

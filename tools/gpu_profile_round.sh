@@ -9,11 +9,11 @@ OUT=$ROOT/gpurun_out/prof_$ROUND
 rm -rf $OUT; mkdir -p $OUT
 python3 $ROOT/tools/stamp.py > $OUT/source_stamp.txt
 cd /tmp && export TMPDIR=/tmp
-BARGS="--steps 200 --warmup 20 --no-cpu-baseline --no-extra"
+BARGS="--full --steps 200 --warmup 20 --no-cpu-baseline --no-extra"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $BARGS > $OUT/bench_under_rocprofv3.json 2> $OUT/trace.err
 for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"; do
   name=$(echo $pass | tr ' ' '_' | cut -c1-30)
-  timeout 400 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/pmc_$name -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > /dev/null 2> $OUT/pmc_$name.err
+  timeout 400 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $OUT/pmc_$name -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra > /dev/null 2> $OUT/pmc_$name.err
 done
 # the one-launch form: float32 by name and the uint8 front door (kernel stats + HBM traffic)
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_persist -- python3 $ROOT/tools/bench_reinhard_persist.py > $OUT/trace_persist.txt 2>&1
@@ -48,6 +48,6 @@ python3 tools/summarize_pmc.py $OUT/mfma_gm960 ct:: _all > $OUT/gmflow_960x540_m
 # keep what is small enough to travel back (the raw traces of the CNN runs are large)
 find $OUT -name "*kernel_trace.csv" -size +20M -delete
 find $OUT/mfma_dc1080 $OUT/mfma_gm960 -name "*counter_collection.csv" -size +20M -delete
-timeout 900 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_20_5.json 2> $OUT/bench_20_5.err
+timeout 900 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_20_5.json 2> $OUT/bench_20_5.err
 tail -c 600 $OUT/bench_default.json
