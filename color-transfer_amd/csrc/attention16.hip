@@ -95,12 +95,17 @@ __device__ __forceinline__ void xcd_order(int &bx, int &by) {
     bx = (int)(vid % gx); by = (int)(vid / gx);
 }
 
-template <int C, int CV, bool MAP>
+// IDX (rows64 only: no map, no key split): also the expected matching column, disp[b][i] = i - sum_j P_ij j (pasmnet/utils.py:65-67),
+// accumulated in the offset form sum_j p_j (j - i) beside the softmax sum l and rescaled with it (no i - E[j] cancellation at large
+// columns); the P.V arithmetic is the same code, so `out` is bitwise that of the IDX = false kernel.
+template <int C, int CV, bool MAP, bool IDX = false>
 __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                                     const float *__restrict__ v, const int *__restrict__ region,
                                                                     const int *__restrict__ rowmap, float *__restrict__ out,
                                                                     float *__restrict__ stats, int L, float scale,
-                                                                    float *__restrict__ part, long long kv_shift, long long kv_total) {
+                                                                    float *__restrict__ part, long long kv_shift, long long kv_total,
+                                                                    float *__restrict__ disp) {
+    static_assert(!IDX || !MAP, "the expected index is built for the unmapped rows");
     constexpr bool PVS = CV >= 32;                  // values on the matrix pipe
     constexpr int NVT = PVS ? CV / 32 : 1;
     constexpr int KV4 = (32 * C / 4) / 256;         // float4 per thread of one K tile
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
         if (region && tid < 32) Rs[tid] = rpre;
     };
 
-    float m_run = -INFINITY, l_run = 0.f;
+    float m_run = -INFINITY, l_run = 0.f, a_run = 0.f;     // a_run: sum_j p_j (j - i) in the domain of l_run (IDX)
     f32x16h o[NVT];
     float o2x = 0.f, o2y = 0.f;
     if constexpr (PVS) {
@@ -336,6 +341,15 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
         psum += __shfl_xor(psum, 32, 64);
         l_run = l_run * corr + psum;
         m_run = m_new;
+        if constexpr (IDX) {
+            // key of register r minus the query, exact in float32: (j0 + 4 hl - qi) + (r&3) + 8(r>>2)
+            const float d0 = (float)(j0 + 4 * hl - qi);
+            float asum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) asum = fmaf(s[r], d0 + (float)((r & 3) + 8 * (r >> 2)), asum);
+            asum += __shfl_xor(asum, 32, 64);
+            a_run = a_run * corr + asum;
+        }
         if constexpr (PVS) {
             // the accumulators live in the domain 2^(e_cur + 15); a new running V exponent rides on the softmax correction
             const float ce = __builtin_amdgcn_ldexpf(corr, e_stage - e_cur);
@@ -407,6 +421,9 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
         return;
     }
     const float inv = 1.0f / l_run;
+    if constexpr (IDX) {
+        if (qlive && hl == 0) disp[tb + qi] = -a_run / l_run;
+    }
     if (stats && qlive && hl == 0) {     // row statistics of the softmax (max, sum): used by the column-sum pass
         stats[(tb + qi) * 2] = m_run * kLn2H;   // natural-log units for the column-sum kernel
         stats[(tb + qi) * 2 + 1] = __builtin_amdgcn_ldexpf(l_run, -(int)POFF);
@@ -565,7 +582,7 @@ void attention16_tokens128(const float *q, const float *k, const float *v, const
                            int len, int cv, float scale, int nsplit, float *ws, long long kv_shift, long long kv_total, hipStream_t s) {
     dim3 grid((len + 127) / 128, batch, nsplit);
     float *nostats = nullptr;
-#define CT_ATT16(CVV, MAPPED) hipLaunchKernelGGL((attention16_tokens_kernel<128, CVV, MAPPED>), grid, dim3(256), 0, s, q, k, v, region, rowmap, out, nostats, len, scale, ws, kv_shift, kv_total)
+#define CT_ATT16(CVV, MAPPED) hipLaunchKernelGGL((attention16_tokens_kernel<128, CVV, MAPPED>), grid, dim3(256), 0, s, q, k, v, region, rowmap, out, nostats, len, scale, ws, kv_shift, kv_total, (float *)nullptr)
     if (cv == 128) { if (rowmap) CT_ATT16(128, true); else CT_ATT16(128, false); }
     else { if (rowmap) CT_ATT16(2, true); else CT_ATT16(2, false); }
 #undef CT_ATT16
@@ -575,8 +592,17 @@ void attention16_rows64(const float *q, const float *k, const float *v, float *o
                         hipStream_t s) {
     dim3 grid((len + 127) / 128, batch);
     const int *noreg = nullptr;
-    if (v) hipLaunchKernelGGL((attention16_tokens_kernel<64, 96, false>), grid, dim3(256), 0, s, q, k, v, noreg, noreg, out, stats, len, scale, (float *)nullptr, 0LL, 0LL);
-    else hipLaunchKernelGGL((attention16_tokens_kernel<64, 0, false>), grid, dim3(256), 0, s, q, k, v, noreg, noreg, out, stats, len, scale, (float *)nullptr, 0LL, 0LL);
+    if (v) hipLaunchKernelGGL((attention16_tokens_kernel<64, 96, false>), grid, dim3(256), 0, s, q, k, v, noreg, noreg, out, stats, len, scale, (float *)nullptr, 0LL, 0LL, (float *)nullptr);
+    else hipLaunchKernelGGL((attention16_tokens_kernel<64, 0, false>), grid, dim3(256), 0, s, q, k, v, noreg, noreg, out, stats, len, scale, (float *)nullptr, 0LL, 0LL, (float *)nullptr);
+}
+
+void attention16_rows64_disp(const float *q, const float *k, const float *v, float *out, float *disp, int batch, int len, float scale,
+                             hipStream_t s) {
+    dim3 grid((len + 127) / 128, batch);
+    const int *noreg = nullptr;
+    float *nostats = nullptr;
+    if (v) hipLaunchKernelGGL((attention16_tokens_kernel<64, 96, false, true>), grid, dim3(256), 0, s, q, k, v, noreg, noreg, out, nostats, len, scale, (float *)nullptr, 0LL, 0LL, disp);
+    else hipLaunchKernelGGL((attention16_tokens_kernel<64, 0, false, true>), grid, dim3(256), 0, s, q, k, v, noreg, noreg, out, nostats, len, scale, (float *)nullptr, 0LL, 0LL, disp);
 }
 
 void attention16_colsum64(const float *q, const float *k, const float *stats, float *colsum, int batch, int len, float scale, hipStream_t s) {

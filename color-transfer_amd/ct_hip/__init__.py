@@ -997,6 +997,9 @@ SIGNATURES.update({
     "ct_rows_to_nchw_f32": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_int, _c_int, _c_p]),
     "ct_attention_rows64_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_f, _c_p]),
     "ct_attention_colsum64_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_f, _c_p]),
+    "ct_attention_rows64_disp_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_f, _c_p]),
+    "ct_pam_disp_fill_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
+    "ct_pam_regress_disp_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
     "ct_local_corr_softmax_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "ct_local_corr_flow_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "ct_local_attn_prop_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
@@ -1492,17 +1495,19 @@ def tokens_to_nchw(t, h, w):
     return out
 
 
-def pam_streaming(q, k, v, rgb, q_other, k_other):
+def pam_streaming(q, k, v, rgb, q_other, k_other, want_disp=False):
     """DCMCS3DI's parallax attention through the streaming kernels (any width):
     q,k [B,64,H,W] = Q(left), K(right); v [B,64,H,W], rgb [B,3,H,W]; q_other,k_other = Q(right), K(left).
-    Returns (fea_warped [B,64,H,W], warped_rgb [B,3,H,W], valid [B,1,H,W] 0/1, colsum [B,1,H,W])."""
+    Returns (fea_warped [B,64,H,W], warped_rgb [B,3,H,W], valid [B,1,H,W] 0/1, colsum [B,1,H,W]), and with want_disp the
+    unfilled disparity disp_ini [B,1,H,W] = i - E[j] under the same attention as a fifth element (pam_streaming_rows)."""
     _f32c(q, k, v, rgb, q_other, k_other)
     b, c, h, w = q.shape
     if c != 64 or v.shape[1] != 64:
         raise CtHipError("pam_streaming is built for 64 channels")
     vt = torch.empty((b * h, w, 96), dtype=torch.float32, device=q.device)
     nchw_to_rows(v, vt, 0)
-    return pam_streaming_rows(nchw_to_rows(q), nchw_to_rows(k), vt, rgb, nchw_to_rows(q_other), nchw_to_rows(k_other))
+    return pam_streaming_rows(nchw_to_rows(q), nchw_to_rows(k), vt, rgb, nchw_to_rows(q_other), nchw_to_rows(k_other),
+                              want_disp=want_disp)
 
 
 def nchw_to_rows(t, out=None, c0=0):
@@ -1514,9 +1519,11 @@ def nchw_to_rows(t, out=None, c0=0):
     return out
 
 
-def pam_streaming_rows(qt, kt, vt, rgb, qo, ko):
+def pam_streaming_rows(qt, kt, vt, rgb, qo, ko, want_disp=False):
     """pam_streaming on token rows: qt, kt, qo, ko [B*H, W, 64] (contiguous; views of a larger rows tensor along dim 0 are fine);
-    vt [B*H, W, 96] with the value in channels 0..63 -- channels 64..95 are filled here (rgb [B,3,H,W] + zero padding)."""
+    vt [B*H, W, 96] with the value in channels 0..63 -- channels 64..95 are filled here (rgb [B,3,H,W] + zero padding).
+    want_disp: the attend pass also accumulates the expected matching column (ct_attention_rows64_disp_f32, same `out` bit for
+    bit) and disp_ini [B,1,H,W] is returned as a fifth element."""
     b, _, h, w = rgb.shape
     for t in (qt, kt, qo, ko):
         if t.shape != (b * h, w, 64) or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda:
@@ -1533,13 +1540,80 @@ def pam_streaming_rows(qt, kt, vt, rgb, qo, ko):
     vt[:, :, 67:] = 0.0                               # the 29 padding channels of the 96-channel value
     nchw_to_rows(rgb, vt, 64)
     out = torch.empty((b * h, w, 96), dtype=torch.float32, device=qt.device)
-    check(lib().ct_attention_rows64_f32(_ptr(qt), _ptr(kt), _ptr(vt), _ptr(out), _c_p(0), b * h, w, scale, _stream()))
+    if want_disp:
+        disp_ini = torch.empty((b, 1, h, w), dtype=torch.float32, device=qt.device)
+        check(lib().ct_attention_rows64_disp_f32(_ptr(qt), _ptr(kt), _ptr(vt), _ptr(out), _ptr(disp_ini), b * h, w, scale, _stream()))
+    else:
+        check(lib().ct_attention_rows64_f32(_ptr(qt), _ptr(kt), _ptr(vt), _ptr(out), _c_p(0), b * h, w, scale, _stream()))
     fea = nchw(out, 64, 0)
     wrgb = nchw(out, 3, 64)
-    stats = torch.empty((b * h, w, 2), dtype=torch.float32, device=qt.device)
+    valid, colsum = pam_valid_rows(qo, ko, b, h, w)
+    if want_disp:
+        return fea, wrgb, valid, colsum, disp_ini
+    return fea, wrgb, valid, colsum
+
+
+def pam_valid_rows(qo, ko, b, h, w):
+    """valid mask of the left view from the streaming kernels: qo = Q(right), ko = K(left) as token rows [B*H, W, 64].
+    Returns (valid [B,1,H,W] 0/1, colsum [B,1,H,W])."""
+    scale = 1.0 / 64
+    stats = torch.empty((b * h, w, 2), dtype=torch.float32, device=qo.device)
     check(lib().ct_attention_rows64_f32(_ptr(qo), _ptr(ko), _c_p(0), _c_p(0), _ptr(stats), b * h, w, scale, _stream()))
-    colsum = torch.empty((b * h, w), dtype=torch.float32, device=qt.device)
+    colsum = torch.empty((b * h, w), dtype=torch.float32, device=qo.device)
     check(lib().ct_attention_colsum64_f32(_ptr(qo), _ptr(ko), _ptr(stats), _ptr(colsum), b * h, w, scale, _stream()))
     colsum = colsum.view(b, 1, h, w)
     valid = (colsum > 0.1).float()                    # threshold only (utils.py:34); the sums come from the kernel
-    return fea, wrgb, valid, colsum
+    return valid, colsum
+
+
+# ------------------------------------------------------------------------------------------------
+# Disparity of the parallax attention (pasmnet/utils.py:55-105; csrc/disparity.hip)
+# ------------------------------------------------------------------------------------------------
+def attention_rows64_index(qt, kt, b, h, w):
+    """disp_ini [B,1,H,W] = i - sum_j softmax_j(q_i.k_j / 64) j from token rows qt, kt [B*H, W, 64] (the index-only streaming pass)"""
+    for t in (qt, kt):
+        if t.shape != (b * h, w, 64):
+            raise CtHipError("attention_rows64_index needs [B*H, W, 64] token rows")
+    _f32c(qt, kt)
+    disp_ini = torch.empty((b, 1, h, w), dtype=torch.float32, device=qt.device)
+    check(lib().ct_attention_rows64_disp_f32(_ptr(qt), _ptr(kt), _c_p(0), _c_p(0), _ptr(disp_ini), b * h, w, 1.0 / 64, _stream()))
+    return disp_ini
+
+
+def _mask_f32(valid, shape, name):
+    if not torch.is_tensor(valid) or not valid.is_cuda:
+        raise CtHipError("%s: the mask must be a CUDA tensor (no CPU path)" % name)
+    _check_device(valid)
+    if tuple(valid.shape) != tuple(shape):
+        raise CtHipError("%s: mask of shape %s, expected %s" % (name, tuple(valid.shape), tuple(shape)))
+    return valid.to(torch.float32).contiguous()
+
+
+def pam_disp_fill(disp_ini, valid):
+    """The occlusion fill of regress_disp (utils.py:85-105) on disp_ini [B,1,H,W]: valid pixels keep disp_ini, an invalid pixel k
+    steps right of a valid one gets its value divided k times by float32 (1 + 1e-4), the hole at a row's start likewise from the
+    row's first valid pixel, a row without valid pixels 0.  valid: bool or 0/1 float [B,1,H,W]."""
+    _f32c(disp_ini)
+    if disp_ini.dim() != 4 or disp_ini.shape[1] != 1:
+        raise CtHipError("pam_disp_fill needs disp_ini of shape [B,1,H,W]")
+    valid = _mask_f32(valid, disp_ini.shape, "pam_disp_fill")
+    b, _, h, w = disp_ini.shape
+    out = torch.empty_like(disp_ini)
+    check(lib().ct_pam_disp_fill_f32(_ptr(disp_ini), _ptr(valid), _ptr(out), b, h, w, _stream()))
+    return out
+
+
+def regress_disp(att, valid):
+    """pasmnet/utils.py:55-105 on the GPU: att [B,H,W,W] float32 (rows need not sum to 1), valid bool or 0/1 float [B,1,H,W]
+    -> disp [B,1,H,W] float32.  One pass over att (i - sum_j att_ij j, fixed order), then the row fill of pam_disp_fill."""
+    if not torch.is_tensor(att) or not att.is_cuda:
+        raise CtHipError("regress_disp runs on the GPU only (no CPU fallback)")
+    if att.dim() != 4 or att.shape[2] != att.shape[3]:
+        raise CtHipError("regress_disp needs att of shape [B,H,W,W]")
+    att = att.to(torch.float32).contiguous()
+    _f32c(att)
+    b, h, w, _ = att.shape
+    valid = _mask_f32(valid, (b, 1, h, w), "regress_disp")
+    out = torch.empty((b, 1, h, w), dtype=torch.float32, device=att.device)
+    check(lib().ct_pam_regress_disp_f32(_ptr(att), _ptr(valid), _ptr(out), b, h, w, _stream()))
+    return out

@@ -8,6 +8,8 @@ other convolutions in ct_conv2d_split_f32 (three bf16 pieces) -- or all of them 
 (exact-f32 MFMA) in `exact` mode; the parallax attention in the streaming kernels behind
 ct_hip.pam_streaming (ct_pam_attend_f32 / ct_pam_valid_f32 when the [B,H,W,W] maps are wanted); torch
 only allocates tensors.  Training (`step`, losses, logging: dcmcs3di.py:68-147) is out of scope.
+`disparity(left, right)` gives the left view's disparity of the reference's log_images (dcmcs3di.py:126,
+pasmnet/utils.py:55-105) from the streaming attention, at any width and without a [B,H,W,W] map.
 No CPU fallback.
 """
 import torch
@@ -51,8 +53,10 @@ class DCMCS3DI(torch.nn.Module):
         self.transfer.append(torch.nn.Conv2d(channels // 2, 3, kernel_size=3, padding=1))
 
     @torch.no_grad()
-    def forward_parts(self, left, right, want_att=False, want_valid_right=False):
-        """The forward pass with its intermediates (used by forward() and by the parity tests)."""
+    def forward_parts(self, left, right, want_att=False, want_valid_right=False, want_disp=False):
+        """The forward pass with its intermediates (used by forward() and by the parity tests).  want_disp adds disp_ini_left
+        (i - E[j] under att_r2l) and disp_left (regress_disp's occlusion fill of it under valid_left), [B,1,H,W] float32; every
+        other part is bitwise the same as without it."""
         if not left.is_cuda:
             raise ct_hip.CtHipError("DCMCS3DI runs on the GPU only (no CPU fallback)")
         left = left.contiguous().float()
@@ -82,6 +86,12 @@ class DCMCS3DI(torch.nn.Module):
             fea_warped, warped_rgb, att_r2l = ct_hip.pam_attend(q[:B].contiguous(), k[B:].contiguous(), v, right, want_att=want_att)
             # left-to-right softmax, column sums -> valid mask of the LEFT view (utils.py:31,34-35)
             valid_left, colsum_left, att_l2r = ct_hip.pam_valid(q[B:].contiguous(), k[:B].contiguous(), want_att=want_att)
+            if want_disp and want_att:
+                # one pass over the materialised map; an all-valid mask leaves the unfilled disparity
+                disp_ini_left = ct_hip.regress_disp(att_r2l, torch.ones_like(valid_left))
+            elif want_disp:
+                # the index-only streaming pass on the zero-padded 64-channel query / key rows (zero channels add nothing to a score)
+                disp_ini_left = ct_hip.attention_rows64_index(ct_hip.nchw_to_rows(q[:B]), ct_hip.nchw_to_rows(k[B:]), B, H, W)
         else:
             # streaming (online-softmax) kernels: no score tile in LDS, any width, K/V rows fetched with 16-byte loads.  They read
             # token rows [B*H, W, C]; the three 1x1 convolutions store that layout from their epilogues (no NCHW q/k/v, no
@@ -91,7 +101,10 @@ class DCMCS3DI(torch.nn.Module):
             kt = conv_forward_rows(self.matcher.key, head)
             vt = conv_forward_rows(self.matcher.value, fea_right, channels=96)
             n = B * H
-            fea_warped, warped_rgb, valid_left, colsum_left = ct_hip.pam_streaming_rows(qt[:n], kt[n:], vt, right, qt[n:], kt[:n])
+            res = ct_hip.pam_streaming_rows(qt[:n], kt[n:], vt, right, qt[n:], kt[:n], want_disp=want_disp)
+            fea_warped, warped_rgb, valid_left, colsum_left = res[:4]
+            if want_disp:
+                disp_ini_left = res[4]                                     # from the attend pass itself
         # dcmcs3di.py:59,47: transfer[0] (1x1, 129 -> 64) reads cat([fea_left, fea_warped, valid_left]) straight from its
         # three tensors (a three-source K loop in ct_conv2d_split_f32; the 129-channel tensor is never built)
         x = conv_forward(self.transfer[0], fea_left, x2=fea_warped, x3=valid_left)
@@ -105,7 +118,39 @@ class DCMCS3DI(torch.nn.Module):
                      pre_clamp=pre_clamp, corrected=pre_clamp.clamp(min=0, max=1))
         if want_valid_right:
             parts["valid_right"], parts["colsum_right"], _ = ct_hip.pam_valid(q[:B], k[B:])
+        if want_disp:
+            parts["disp_ini_left"] = disp_ini_left
+            parts["disp_left"] = ct_hip.pam_disp_fill(disp_ini_left, valid_left)
         return parts
+
+    @torch.no_grad()
+    def disparity(self, left, right):
+        """Disparity of the left view (the reference's regress_disp(att_right2left, valid_mask_left), dcmcs3di.py:126) at
+        inference: (disp_left [B,1,H,W] float32, valid_left [B,1,H,W] bool).  Streaming kernels only -- the feature extractor,
+        the attention head, the index-only attention pass and the valid-mask passes -- so any width, no [B,H,W,W] tensor and no
+        colour-transfer half.  For 16 / 32 / 48 channels the query / key are zero-padded to 64 as in forward_parts."""
+        if not left.is_cuda:
+            raise ct_hip.CtHipError("DCMCS3DI runs on the GPU only (no CPU fallback)")
+        left = left.contiguous().float()
+        right = right.contiguous().float()
+        B, H, W = left.shape[0], left.shape[2], left.shape[3]
+        fea = sequential_forward(self.extraction, torch.cat([left, right], dim=0))
+        head = resb_forward(self.matcher.head, fea)
+        if self.hparams.channels == 64:
+            qt = conv_forward_rows(self.matcher.query, head)               # [2B*H, W, 64]
+            kt = conv_forward_rows(self.matcher.key, head)
+        else:
+            q = conv_forward(self.matcher.query, head)
+            k = conv_forward(self.matcher.key, head)
+            c = q.shape[1]
+            q64, k64 = q.new_zeros((q.shape[0], 64) + tuple(q.shape[2:])), k.new_zeros((k.shape[0], 64) + tuple(k.shape[2:]))
+            q64[:, :c] = q * (64.0 / c)
+            k64[:, :c] = k
+            qt, kt = ct_hip.nchw_to_rows(q64), ct_hip.nchw_to_rows(k64)
+        n = B * H
+        disp_ini = ct_hip.attention_rows64_index(qt[:n], kt[n:], B, H, W)   # Q(left) . K(right)
+        valid, _ = ct_hip.pam_valid_rows(qt[n:], kt[:n], B, H, W)         # Q(right) . K(left) column sums
+        return ct_hip.pam_disp_fill(disp_ini, valid), valid > 0.5
 
     def forward(self, left, right, inference=False, return_attention=None):
         """Same return structure as the reference (dcmcs3di.py:61-66):

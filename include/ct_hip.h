@@ -460,6 +460,24 @@ int ct_attention_rows64_f32(const float *q, const float *k, const float *v, floa
                             int batch, int len, float scale, void *stream);
 int ct_attention_colsum64_f32(const float *q, const float *k, const float *stats, float *colsum,
                               int batch, int len, float scale, void *stream);
+/* Disparity of the parallax attention (pasmnet/utils.py:55-105, regress_disp; csrc/disparity.hip).  Argument checks return
+ * CT_E_BADARG before anything touches the device: a negative size, a null pointer (unless the call is empty: batch / n*h*w == 0 is
+ * a no-op that accepts nulls), w > 32768 (the fill entries).
+ *   ct_attention_rows64_disp_f32: ct_attention_rows64_f32 plus disp_ini[b][i] = i - sum_j softmax_j(q_i.k_j*scale) j, [batch][len],
+ *       accumulated as sum_j P_ij (j - i) inside the streaming pass.  v != NULL: `out` exactly as ct_attention_rows64_f32(q, k, v,
+ *       out, NULL, ...) writes it under the same settings (CT_HIP_ATT16 included), in the same pass; v == NULL (out ignored): the
+ *       expected index alone.  No statistics.
+ *   ct_pam_disp_fill_f32: the occlusion fill of regress_disp (utils.py:85-105).  disp_ini, valid, disp: [n][1][h][w] float32,
+ *       valid 0 / 1 (the mask ct_pam_valid_f32 / the streaming path produce).  disp = disp_ini where valid; an invalid pixel k
+ *       pixels right of the last valid pixel p of its row: disp_ini[p] / (1 + 1e-4), k times in float32 (bitwise the reference's
+ *       loops); left of the row's first valid pixel f: disp_ini[f] divided (f - x) times; a row without a valid pixel: 0.
+ *       disp may be disp_ini (in place).
+ *   ct_pam_regress_disp_f32: regress_disp of a materialised att [n][h][w][w] (P[i][j], rows need not sum to 1):
+ *       disp_ini = i - sum_j att[i][j] j in a fixed order, then the fill above, into disp [n][1][h][w].                  */
+int ct_attention_rows64_disp_f32(const float *q, const float *k, const float *v, float *out, float *disp_ini,
+                                 int batch, int len, float scale, void *stream);
+int ct_pam_disp_fill_f32(const float *disp_ini, const float *valid, float *disp, int n, int h, int w, void *stream);
+int ct_pam_regress_disp_f32(const float *att, const float *valid, float *disp, int n, int h, int w, void *stream);
 /* matching.py:42-86: flow[b][2][h][w] from the softmax over the (2r+1)^2 integer neighbourhood; f0,f1 tokens       */
 int ct_local_corr_softmax_f32(const float *f0, const float *f1, float *flow, int batch, int h, int w,
                               int radius, void *stream);
