@@ -57,6 +57,7 @@ SIGNATURES = {
     "ct_mk_f64_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_sz, _c_p]),
     "ct_frame_psnr_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
     "ct_distort_u8": (_c_int, [_c_p, _c_int, _c_int, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_pack_u8_f32": (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p]),
     "ct_regrain_workspace_bytes": (_c_sz, [_c_int, _c_int]),
     "ct_regrain_f64": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_sz, _c_p]),
     "ct_metric_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
@@ -432,6 +433,43 @@ def distort_u8(img, kind, param, want_u8=False):
         raise ValueError("distortion %r: parameter %r out of range" % (kind, param))      # torchvision raises ValueError too
     check(rc)
     return (out_f, out_u) if want_u8 else out_f
+
+
+CT_PACK_HWC, CT_PACK_CHW = 0, 1
+PACK_LAYOUTS = {"hwc": CT_PACK_HWC, "chw": CT_PACK_CHW}
+
+
+def pack_u8(x, layout=None, out=None):
+    """Corrected float32 frames -> uint8 [n,H,W,3]: rint(clamp(x, 0, 1) * 255), ties to even, NaN -> 0 (ct_pack_u8_f32; the
+    reference's img_as_ubyte(x.clip(0, 1)), utils/postprocess.py:138).  x: [n,3,H,W] ("chw") or [n,H,W,3] ("hwc"), or one
+    frame of either as a 3-D tensor.  layout is inferred from the shape and required when both readings fit.  out: an optional
+    preallocated uint8 [n,H,W,3] tensor on the same device.  Asynchronous on the current stream; nothing is allocated with out."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4):
+        raise CtHipError("pack_u8 needs a [n,3,H,W] / [n,H,W,3] tensor or one frame of either")
+    _require_cuda(x)
+    if x.dtype != torch.float32:
+        raise CtHipError("pack_u8 needs float32 frames (got %s)" % x.dtype)
+    xb = x if x.dim() == 4 else x.unsqueeze(0)
+    chw, hwc = xb.shape[1] == 3, xb.shape[3] == 3
+    if layout is None:
+        if chw == hwc:
+            raise CtHipError("pack_u8: %s of shape %s; pass layout='chw' or 'hwc'"
+                             % ("both layouts fit a tensor" if chw else "neither layout fits a tensor", tuple(x.shape)))
+        layout = "chw" if chw else "hwc"
+    if layout not in PACK_LAYOUTS or not (chw if layout == "chw" else hwc):
+        raise CtHipError("pack_u8: layout %r does not fit shape %s" % (layout, tuple(x.shape)))
+    n = xb.shape[0]
+    h, w = (xb.shape[2], xb.shape[3]) if layout == "chw" else (xb.shape[1], xb.shape[2])
+    shape = (n, h, w, 3) if x.dim() == 4 else (h, w, 3)               # one frame in, one frame out
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != x.device or tuple(out.shape) not in (shape, (n, h, w, 3)):
+            raise CtHipError("pack_u8: out must be a uint8 %s tensor on %s" % (list(shape), x.device))
+        _require_cuda(out)
+    if x.numel():
+        check(lib().ct_pack_u8_f32(_ptr(xb), PACK_LAYOUTS[layout], n, h, w, _ptr(out), _stream()))
+    return out
 
 
 def regrain(img_in, img_col, nbits=(4, 16, 32, 64, 64, 64), out=None):

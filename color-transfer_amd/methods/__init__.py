@@ -80,6 +80,16 @@ class Runner(torch.nn.Module):
         ct_hip.reinhard_persist(group_u8[0], group_u8[1], gt=group_u8[2], out=self._out[:k], psnr_out=psnr_out)
         return self._out[:k]
 
+    def predict_group(self, group_u8):
+        """group_u8 as for test_group ([2 or 3 roles: target, reference(, gt)][k][H][W][3], gt is not read) -> the corrected frames,
+        float32 [k][H][W][3], from ONE asynchronous call; the buffer is reused by the next call (stream order keeps a reader
+        on the same stream safe).  `utils.cli predict` packs them to bytes with ct_hip.pack_u8."""
+        import ct_hip
+        k = group_u8.shape[1]
+        if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:
+            self._out = torch.empty((k,) + tuple(group_u8.shape[2:]), dtype=torch.float32, device=group_u8.device)
+        return ct_hip.reinhard_persist(group_u8[0], group_u8[1], out=self._out[:k])
+
     def forward(self, batch):
         target, reference = batch["target"], batch["reference"]
         if self.func_cuda is not None and target.is_cuda:

@@ -1,15 +1,22 @@
 """`python -m utils.cli test --config <yaml> [--model.func_spec ...] [--data.n_frames N] [--ckpt_path P]`
+`python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--writer.depth D] [--writer.workers N] [...]`
 
 A minimal look-alike of the reference's LightningCLI entry point (utils/cli.py:1-3, README.md:69-71) for the
-`test` sub-command only (Lightning/jsonargparse are not part of this stack): YAML with `class_path/init_args`
+`test` and `predict` sub-commands (Lightning/jsonargparse are not part of this stack): YAML with `class_path/init_args`
 for model and data, dotted `--section.key value` overrides, `trainer.*` keys accepted and ignored.  Frames are
-sharded over ranks when launched with torch.distributed.run (frame f -> rank f % world) and the per-frame
-metrics (PSNR, SSIM, FSIM, iCID: the reference's Test PSNR / Test SSIM / Test FSIM / Test iCID) are gathered with ONE collective
-(utils/sharding.py); rank 0 prints their means.
+sharded over ranks when launched with torch.distributed.run (frame f -> rank f % world).
+
+`test`: the per-frame metrics (PSNR, SSIM, FSIM, iCID: the reference's Test PSNR / Test SSIM / Test FSIM / Test iCID) are gathered
+with ONE collective (utils/sharding.py); rank 0 prints their means.
+
+`predict`: the corrected frames themselves, as bytes -- rint(clamp(x, 0, 1) * 255) on the device (ct_hip.pack_u8, the reference's
+img_as_ubyte(x.clip(0, 1)), utils/postprocess.py:138-144), downloaded through a ring of pinned buffers and written by frame index
+(utils/writer.py): every rank writes its own frames into the one directory, the result does not depend on the world size.
 """
 import importlib
 import os
 import sys
+import types
 
 import torch
 import yaml
@@ -34,14 +41,14 @@ def _instantiate(section):
     return getattr(importlib.import_module(module), cls)(**section.get("init_args", {}))
 
 
-def main(argv=None, timing=None):
-    """timing: None, or a dict that receives {"seconds", "frames", "frames_local", "h2d_bytes"} of the first loader's loop --
-    barrier + synchronize on both sides, the gather inside, an untimed first pass over a few groups before it (code objects,
-    clocks, the communicator) -- for bench.py's configs[4] leg, which measures THIS entry point rather than a loop of its own."""
-    argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] != "test":
-        raise SystemExit("only the `test` sub-command exists here (fit/validate/predict are Lightning training paths)")
-    cfg, ckpt, i = {}, None, 1
+def quantise_u8(x):
+    """ct_hip.pack_u8's rule in torch, for the CT_CLI_DEVICE=cpu test mode only (torch.round is ties-to-even)"""
+    return (x.clamp(0, 1).nan_to_num(0) * 255).round().to(torch.uint8)
+
+
+def _parse(argv):
+    """argv after the sub-command -> (cfg, ckpt_path, {"output", "format"}); everything else is a dotted override of the YAML"""
+    cfg, ckpt, opts, i = {}, None, {}, 1
     if (len(argv) - 1) % 2:
         raise SystemExit("arguments come in `--key value` pairs; got a dangling %r" % argv[-1])
     while i < len(argv):
@@ -51,9 +58,16 @@ def main(argv=None, timing=None):
                 cfg = yaml.safe_load(fh) or {}
         elif key == "--ckpt_path":
             ckpt = val
+        elif argv[0] == "predict" and key in ("--output", "--format"):
+            opts[key[2:]] = val
         elif key.startswith("--"):
             _set(cfg, key[2:], val)
         i += 2
+    return cfg, ckpt, opts
+
+
+def _setup(cfg, ckpt):
+    """what `test` and `predict` share: rank / device selection, the process group, the model (+ checkpoint) and the loaders"""
     import torch.distributed as dist
     from utils import sharding as sh
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -92,12 +106,7 @@ def main(argv=None, timing=None):
     data_cfg = dict(cfg.get("data", {}))
     data_cfg["class_path"] = "utils.data.DataModule"
     dm = _instantiate(data_cfg)
-    from methods import METRICS, fsim, icid, psnr, ssim
-    from utils.data import prefetch, prefetch_groups
-    # the reference's test_dataloader() returns [artificial, real-world] (utils/data.py:168-179) and Lightning logs each
-    # metric once per loader ("Test PSNR/dataloader_idx_1"); a single loader prints the bare names like Lightning does
     loaders = dm.test_dataloader()
-    tables = []
 
     def fence():
         if world > 1:
@@ -105,6 +114,46 @@ def main(argv=None, timing=None):
         if not on_cpu:
             torch.cuda.synchronize()
 
+    return types.SimpleNamespace(rank=rank, world=world, on_cpu=on_cpu, device=device, own_group=own_group, model=model,
+                                 loaders=loaders, fence=fence)
+
+
+def main(argv=None, timing=None):
+    """`test` returns the [n_frames, 4] metric table of the first loader, `predict` the number of frames written.
+    timing: None, or a dict that receives {"seconds", "frames", "frames_local", "h2d_bytes"} of the first loader's loop --
+    barrier + synchronize on both sides, the gather inside, an untimed first pass over a few groups before it (code objects,
+    clocks, the communicator) -- for bench.py's configs[4] leg, which measures THIS entry point rather than a loop of its own.
+    `predict` fills it the same way (+ "d2h_bytes"), the writer's drain inside the measurement."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if not argv or argv[0] not in ("test", "predict"):
+        raise SystemExit("only the `test` and `predict` sub-commands exist here (fit/validate are Lightning training paths)")
+    cfg, ckpt, opts = _parse(argv)
+    if argv[0] == "predict":
+        from utils.writer import FORMATS
+        if not opts.get("output"):
+            raise SystemExit("predict needs `--output DIR`: the directory the corrected frames are written to")
+        if opts.setdefault("format", "png") not in FORMATS:
+            raise SystemExit("--format %r: one of %s" % (opts["format"], ", ".join(FORMATS)))
+    ctx = _setup(cfg, ckpt)
+    import torch.distributed as dist
+    try:
+        if argv[0] == "predict":
+            return _predict(ctx, opts["output"], opts["format"], cfg.get("writer") or {}, timing)
+        return _test(ctx, timing)
+    finally:
+        if ctx.own_group:
+            dist.destroy_process_group()
+
+
+def _test(ctx, timing):
+    import torch.distributed as dist
+    from utils import sharding as sh
+    from methods import METRICS, fsim, icid, psnr, ssim
+    from utils.data import prefetch, prefetch_groups
+    rank, world, on_cpu, device, model, loaders, fence = ctx.rank, ctx.world, ctx.on_cpu, ctx.device, ctx.model, ctx.loaders, ctx.fence
+    # the reference's test_dataloader() returns [artificial, real-world] (utils/data.py:168-179) and Lightning logs each
+    # metric once per loader ("Test PSNR/dataloader_idx_1"); a single loader prints the bare names like Lightning does
+    tables = []
     for li, frames in enumerate(loaders):
         mine = sh.frames_of_rank(len(frames), rank, world)
         grouped = (not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "test_group") and model.takes_groups())
@@ -164,10 +213,90 @@ def main(argv=None, timing=None):
             for j, (i, name) in enumerate(cols):
                 print("%s%s: %.4f" % (name, suffix, float(table[:, i].mean())), end="   " if j + 1 < len(cols) else "")
             print("  (%d frames, %d GPU%s)" % (len(frames), world, "" if world == 1 else "s"))
-    table = tables[0]
-    if own_group:
-        dist.destroy_process_group()
-    return table
+    return tables[0]
+
+
+def _predict(ctx, output, fmt, writer_cfg, timing):
+    import time
+    import torch.distributed as dist
+    from utils import sharding as sh
+    from utils.data import prefetch, prefetch_groups
+    from utils.writer import FrameWriter, truncate_raw
+    rank, world, on_cpu, device, model, loaders, fence = ctx.rank, ctx.world, ctx.on_cpu, ctx.device, ctx.model, ctx.loaders, ctx.fence
+    depth, workers = int(writer_cfg.get("depth", 3)), int(writer_cfg.get("workers", 4))
+    if not on_cpu:
+        import ct_hip
+    written = 0
+    for li, frames in enumerate(loaders):
+        out_dir = os.path.join(output, "idx_%d" % li) if len(loaders) > 1 else output
+        mine = sh.frames_of_rank(len(frames), rank, world)
+        grouped = (not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "predict_group") and model.takes_groups())
+        if rank == 0:
+            os.makedirs(out_dir, exist_ok=True)
+            if fmt == "raw":
+                truncate_raw(out_dir)                       # once, before any rank opens the file
+        fence()
+        # device uint8 ring, one slot per writer slot: a slot is packed into again only after its download has completed (the
+        # stream waits for the event, the host does not)
+        ring, downloaded = [None] * depth, [None] * depth
+
+        def pack(n, x, layout):
+            k, (h, w) = x.shape[0], (x.shape[1:3] if layout == "hwc" else x.shape[2:4])
+            slot = n % depth
+            if downloaded[slot] is not None:
+                torch.cuda.current_stream(device).wait_event(downloaded[slot])
+            if ring[slot] is None or ring[slot].shape[1:] != (h, w, 3) or ring[slot].shape[0] < k:
+                ring[slot] = torch.empty((k, h, w, 3), dtype=torch.uint8, device=device)       # the old one: record_stream in submit
+            return slot, ct_hip.pack_u8(x, layout, out=ring[slot][:k])
+
+        def run(indices, writer):
+            with torch.no_grad():
+                if grouped:
+                    # uint8 frames in pinned groups: one upload, ONE transfer call, one pack and ONE download per group of k frames
+                    for n, (ids, dev) in enumerate(prefetch_groups(frames, indices, device)):
+                        slot, u8 = pack(n, model.predict_group(dev), "hwc")
+                        downloaded[slot] = writer.submit(ids, u8)
+                    return
+                for n, (f, sample) in enumerate(prefetch(frames, indices, device)):
+                    batch = {k: v.unsqueeze(0) for k, v in sample.items()}
+                    if hasattr(model, "test_step"):             # the Runner interface: what test_step scores (methods/__init__.py:30)
+                        corrected = model(batch).clamp(0, 1)
+                    else:                                       # CNN modules: forward(target, reference, inference=True)
+                        corrected = model(batch["target"], batch["reference"], inference=True)[0]
+                    if on_cpu:
+                        writer.submit([f], quantise_u8(corrected).permute(0, 2, 3, 1).contiguous())
+                        continue
+                    corrected = corrected.float()
+                    hwc = corrected.permute(0, 2, 3, 1)         # Runner.forward hands out a CHW view of HWC memory: no transpose then
+                    slot, u8 = pack(n, hwc, "hwc") if hwc.is_contiguous() else pack(n, corrected.contiguous(), "chw")
+                    downloaded[slot] = writer.submit([f], u8)
+
+        writer = FrameWriter(out_dir, fmt, depth=depth, workers=workers, n_frames=len(frames), device=None if on_cpu else device)
+        with writer:
+            if timing is not None and li == 0:
+                if grouped:
+                    if hasattr(frames, "prepare"):
+                        frames.prepare(mine)                    # the synthetic frames themselves: made before the clock starts
+                    run(mine[:3 * frames.group], writer)        # initialisation, not part of the measurement
+                fence()
+                t0 = time.perf_counter()
+            run(mine, writer)
+            writer.close()                                      # drained: every frame of this rank is in its file
+        fence()
+        if timing is not None and li == 0:
+            dt = time.perf_counter() - t0
+            if world > 1:
+                tmax = torch.tensor([dt], dtype=torch.float64, device=device)
+                dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+                dt = float(tmax.item())
+            per_frame = frames.height * frames.width * 3 if grouped else 0
+            timing.update({"seconds": dt, "frames": len(frames), "frames_local": len(mine), "h2d_bytes": 3 * per_frame * len(mine),
+                           "d2h_bytes": per_frame * len(mine), "grouped": grouped, "frames_per_call": frames.group if grouped else 1})
+        written += len(frames)
+        if rank == 0:
+            suffix = "/dataloader_idx_%d" % li if len(loaders) > 1 else ""
+            print("wrote %d frames to %s (%s, %d GPU%s)%s" % (len(frames), out_dir, fmt, world, "" if world == 1 else "s", suffix))
+    return written
 
 
 if __name__ == "__main__":

@@ -1,0 +1,213 @@
+"""`FrameWriter` -- the download half of the data path: corrected uint8 frames leave the GPU and land in files, the mirror image
+of `utils.data.prefetch_groups` (the reference writes its results with img_as_ubyte + PNG files, utils/postprocess.py:138-144).
+
+    with FrameWriter(out_dir, fmt="png", depth=3, workers=4) as w:
+        done = w.submit([17, 18], frames_u8)        # uint8 [k,H,W,3], device or host; frame numbers name the files
+
+A ring of `depth` PINNED host buffers: `submit` takes the next slot (blocking while its previous frames are still being written:
+that is the back-pressure, host memory stays at `depth` slots), lets a copy stream wait for the caller's stream, issues ONE
+asynchronous copy of the whole group into the slot and returns the copy's event; the caller's stream is never synchronised.
+Worker threads wait for that event, write the slot's frames and release the slot.  Host tensors skip the copy (they are held by
+reference until written: the caller must not modify them).
+
+Files are named by FRAME INDEX (`%06d.png`, `%06d.npy`; `raw`: frame f at offset f*H*W*3 of `frames.rgb`, rgb24, what
+`ffmpeg -f rawvideo -pix_fmt rgb24 -s WxH` reads), so the ranks of a sharded run write disjoint files -- or disjoint ranges of
+the one raw file -- into one directory and the result does not depend on the world size.  `null` downloads and drops.
+
+The first error of a worker (unwritable directory, full disk) is kept and raised from the next `submit` or from `close()`."""
+import os
+import queue
+import threading
+
+import numpy as np
+import torch
+
+FORMATS = ("png", "npy", "raw", "null")
+MAX_WORKERS = 16
+RAW_NAME = "frames.rgb"
+
+
+def frame_name(index, fmt):
+    return "%06d.%s" % (index, fmt)
+
+
+def truncate_raw(out_dir):
+    """Create `out_dir`/frames.rgb empty.  ONE process of a sharded run does this before the others open the file (and before a
+    barrier): the writers themselves never truncate, they only write their frames' ranges."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, RAW_NAME), "wb"):
+        pass
+
+
+class _Slot:
+    def __init__(self):
+        self.buf = None             # pinned uint8 [capacity, H, W, 3] (device frames only)
+        self.frames = None          # what the workers read: a view of buf, or the caller's host tensor
+        self.event = None           # the download of `frames`
+        self.pending = 0            # frames of this slot not yet written
+
+
+class FrameWriter:
+    def __init__(self, out_dir, fmt="png", depth=3, workers=4, n_frames=None, device=None):
+        """workers: an explicit small number (capped at 16), never derived from the machine's CPU count.  n_frames: the length of
+        the video, required for `raw` (the size of the file).  device: the GPU whose frames are submitted (default: the frames')."""
+        if fmt not in FORMATS:
+            raise ValueError("format %r: one of %s" % (fmt, ", ".join(FORMATS)))
+        if int(depth) < 1 or int(workers) < 1:
+            raise ValueError("depth and workers must be >= 1 (got %r, %r)" % (depth, workers))
+        if fmt == "raw" and n_frames is None:
+            raise ValueError("format raw needs n_frames (frame f lives at offset f*H*W*3 of one file)")
+        self.out_dir, self.fmt = os.fspath(out_dir), fmt
+        self.n_frames = None if n_frames is None else int(n_frames)
+        self.device = None if device is None else torch.device(device)
+        self._slots = [_Slot() for _ in range(int(depth))]
+        self._next = 0
+        self._cond = threading.Condition()
+        self._error = None              # the first worker error, until it has been raised
+        self._failed = False            # sticky: after an error nothing more is written
+        self._frame_shape = None            # raw: the one [H, W, 3] of the file
+        self._raw_fd = None
+        self._dir_made = False
+        self._copy_stream = None
+        self._closed = False
+        self._tasks = queue.Queue()
+        self._threads = [threading.Thread(target=self._work, name="FrameWriter-%d" % i) for i in range(min(int(workers), MAX_WORKERS))]
+        for t in self._threads:
+            t.start()
+
+    # ---- caller's side ---------------------------------------------------------------------------------------------------------
+    def submit(self, indices, frames_u8):
+        """Queue frames_u8[j] for writing as frame indices[j].  Returns the event of the download (None for host tensors): a device
+        buffer handed in here may be overwritten by work that waits for it."""
+        if self._closed:
+            raise RuntimeError("FrameWriter is closed")
+        self._raise_pending()
+        indices = [int(i) for i in indices]
+        if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+            raise ValueError("frames must be a uint8 [k,H,W,3] tensor")
+        if len(indices) != frames_u8.shape[0]:
+            raise ValueError("%d frame indices for %d frames" % (len(indices), frames_u8.shape[0]))
+        if any(i < 0 or (self.n_frames is not None and i >= self.n_frames) for i in indices):
+            raise ValueError("frame index outside [0, %s)" % ("inf" if self.n_frames is None else self.n_frames))
+        if self.fmt == "raw":
+            shape = tuple(frames_u8.shape[1:])
+            if self._frame_shape is None:
+                self._frame_shape = shape
+            elif shape != self._frame_shape:
+                raise ValueError("raw video: frames of %s after frames of %s" % (shape, self._frame_shape))
+        if not indices:
+            return None
+        slot = self._slots[self._next]
+        self._next = (self._next + 1) % len(self._slots)
+        with self._cond:                                    # back-pressure: the slot's previous frames are still being written
+            while slot.pending:
+                self._cond.wait()
+        self._raise_pending()
+        k = len(indices)
+        if frames_u8.is_cuda:
+            dev = frames_u8.device
+            if slot.buf is None or slot.buf.shape[1:] != frames_u8.shape[1:] or slot.buf.shape[0] < k:
+                slot.buf = torch.empty(tuple(frames_u8.shape), dtype=torch.uint8, pin_memory=True)
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(device=self.device if self.device is not None else dev)
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(dev))
+            self._copy_stream.wait_event(ready)
+            slot.frames = slot.buf[:k]
+            with torch.cuda.stream(self._copy_stream):
+                slot.frames.copy_(frames_u8, non_blocking=True)
+                slot.event = torch.cuda.Event()
+                slot.event.record(self._copy_stream)
+            frames_u8.record_stream(self._copy_stream)
+        else:
+            slot.frames, slot.event = frames_u8, None
+        slot.pending = k
+        for j, index in enumerate(indices):
+            self._tasks.put((slot, j, index))
+        return slot.event
+
+    def close(self):
+        """Drain the queue, join the workers, close the raw file, raise the first writer error.  Safe to call twice."""
+        if not self._closed:
+            self._closed = True
+            for _ in self._threads:
+                self._tasks.put(None)
+            for t in self._threads:
+                t.join()
+            if self._raw_fd is not None:
+                try:
+                    if not self._failed and self._frame_shape is not None:
+                        # every rank sets the same full size: frames nobody wrote read as zeros, a longer stale file is cut
+                        os.ftruncate(self._raw_fd, self.n_frames * int(np.prod(self._frame_shape)))
+                except OSError as e:
+                    self._failed, self._error = True, e
+                finally:
+                    os.close(self._raw_fd)
+                    self._raw_fd = None
+        self._raise_pending()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:                                               # the caller's own exception wins; the threads are joined all the same
+            try:
+                self.close()
+            except Exception:
+                pass
+        return False
+
+    def _raise_pending(self):
+        with self._cond:
+            err, self._error = self._error, None
+        if err is not None:
+            raise err
+
+    # ---- workers ---------------------------------------------------------------------------------------------------------------
+    def _work(self):
+        while True:
+            task = self._tasks.get()
+            if task is None:
+                return
+            slot, j, index = task
+            try:
+                if not self._failed:                              # after an error the queue is only drained
+                    if slot.event is not None:
+                        slot.event.synchronize()
+                    self._write(index, slot.frames[j])
+            except BaseException as e:                      # kept for the caller: never swallowed
+                with self._cond:
+                    if not self._failed:
+                        self._failed, self._error = True, e
+            finally:
+                with self._cond:
+                    slot.pending -= 1
+                    if slot.pending == 0:
+                        slot.frames = None
+                        self._cond.notify_all()
+
+    def _ensure_dir(self):
+        if not self._dir_made:
+            os.makedirs(self.out_dir, exist_ok=True)
+            self._dir_made = True
+
+    def _write(self, index, frame):
+        if self.fmt == "null":
+            return
+        self._ensure_dir()
+        arr = frame.numpy()
+        if self.fmt == "png":
+            from PIL import Image
+            Image.fromarray(arr).save(os.path.join(self.out_dir, frame_name(index, "png")))
+        elif self.fmt == "npy":
+            np.save(os.path.join(self.out_dir, frame_name(index, "npy")), arr)
+        else:
+            with self._cond:
+                if self._raw_fd is None:
+                    self._raw_fd = os.open(os.path.join(self.out_dir, RAW_NAME), os.O_WRONLY | os.O_CREAT, 0o666)
+            data = memoryview(np.ascontiguousarray(arr)).cast("B")
+            offset, done = index * len(data), 0
+            while done < len(data):
+                done += os.pwrite(self._raw_fd, data[done:], offset + done)

@@ -209,6 +209,18 @@ int ct_regrain_f64(const double *img_in, const double *img_col, double *out, int
 int ct_distort_u8(const uint8_t *in, int height, int width, int kind, double param, uint8_t *out_u8, float *out_f32,
                   void *ws, size_t ws_bytes, void *stream);
 
+/* ---- corrected frames -> bytes (utils/postprocess.py:138-144: img_as_ubyte(x.clip(0, 1)) before the PNGs are written) ----
+ * in: float32, [n][height][width][3] (CT_PACK_HWC: what ct_reinhard_* / the Runner produce) or [n][3][height][width]
+ * (CT_PACK_CHW: the CNN modules, the sample dicts).  out_hwc: uint8 [n][height][width][3] in both layouts.
+ * q = rint(clamp(x, 0, 1) * 255): one float32 multiplication by 255.0f (no fma, no reciprocal), round to nearest with ties to
+ * even; NaN, -inf and negatives give 0, +inf and values above 1 give 255 -- skimage's float32 branch of img_as_ubyte restated
+ * (np.multiply(image, 255, dtype=float32), np.rint, np.clip; parity unpinned: skimage is absent offline).
+ * Sizes and bases off the 16-byte grid take an element-wise path of the same rule; `in` not aligned to 4 bytes: CT_E_ALIGN;
+ * n, height or width < 1, a null pointer or an unknown layout: CT_E_BADARG.  No workspace.  Added under ABI 9.            */
+#define CT_PACK_HWC 0
+#define CT_PACK_CHW 1
+int ct_pack_u8_f32(const float *in, int layout, int n, int height, int width, uint8_t *out_hwc, void *stream);
+
 /* ---- per-frame metric (first step): PSNR as Runner.test_step logs it (methods/__init__.py:32,37) ----
  * a, b: [batch][n_elems] float32 (any layout, same for both); out[i] = {mse, 10 log10(1/mse)} (data range 1).
  * Deterministic float64 reduction.  ws: batch * 1024 doubles (ct_workspace_bytes(CT_WS_LAB_STATS, ., batch) suffices). */
