@@ -58,6 +58,9 @@ SIGNATURES = {
     "ct_frame_psnr_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
     "ct_distort_u8": (_c_int, [_c_p, _c_int, _c_int, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_sz, _c_p]),
     "ct_pack_u8_f32": (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p]),
+    "ct_bicubic_resize_workspace_bytes": (_c_sz, [_c_i64, _c_int, _c_int, _c_int]),
+    "ct_bicubic_resize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_int, ctypes.c_double, ctypes.c_double, _c_int,
+                                       _c_p, _c_sz, _c_p]),
     "ct_regrain_workspace_bytes": (_c_sz, [_c_int, _c_int]),
     "ct_regrain_f64": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_sz, _c_p]),
     "ct_metric_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
@@ -469,6 +472,65 @@ def pack_u8(x, layout=None, out=None):
         _require_cuda(out)
     if x.numel():
         check(lib().ct_pack_u8_f32(_ptr(xb), PACK_LAYOUTS[layout], n, h, w, _ptr(out), _stream()))
+    return out
+
+
+def _pair(v, name, kind):
+    """one value for both axes, or an (h, w) pair"""
+    vs = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    if len(vs) != 2 or any(isinstance(a, bool) or not isinstance(a, kind) for a in vs):
+        raise CtHipError("%s must be one %s or an (h, w) pair of them (got %r)" % (name, "int" if kind == (int,) else "number", v))
+    return vs
+
+
+def resize_geometry(in_hw, size=None, scale_factor=None):
+    """The shape rule of torch.nn.functional.interpolate(align_corners=False) for a [.., h, w] input: ((ho, wo), (scale_h, scale_w)).
+    With scale_factor the output is floor(in * scale_factor) and the source step per output pixel is 1 / scale_factor (the
+    factor itself, not in / out, as torch does without recompute_scale_factor); with size it is in / out.  Exactly one of the two
+    is given; each is one number or an (h, w) pair.  The steps are Python floats (float64) and go to the kernel as such.  Pure
+    Python: no GPU, no library."""
+    if (size is None) == (scale_factor is None):
+        raise CtHipError("exactly one of size and scale_factor must be given")
+    ins = _pair(in_hw, "in_hw", (int,))
+    if min(ins) < 1:
+        raise CtHipError("in_hw must be positive (got %r)" % (in_hw,))
+    if size is not None:
+        outs = _pair(size, "size", (int,))
+        if min(outs) < 1:
+            raise CtHipError("size must be positive (got %r)" % (size,))
+        return (int(outs[0]), int(outs[1])), (ins[0] / outs[0], ins[1] / outs[1])
+    fs = tuple(float(f) for f in _pair(scale_factor, "scale_factor", (int, float)))
+    if not all(0.0 < f < float("inf") for f in fs):
+        raise CtHipError("scale_factor must be positive and finite (got %r)" % (scale_factor,))
+    outs = tuple(int(np.floor(float(i * f))) for i, f in zip(ins, fs))
+    if min(outs) < 1:
+        raise CtHipError("scale_factor %r leaves no pixel of a %d x %d input" % (scale_factor, ins[0], ins[1]))
+    return outs, (1.0 / fs[0], 1.0 / fs[1])
+
+
+def bicubic_resize(x, size=None, scale_factor=None, antialias=False, out=None):
+    """torch.nn.functional.interpolate(x, size / scale_factor, mode="bicubic", align_corners=False, antialias=antialias) on a
+    float32 [n,c,h,w] device tensor (ct_bicubic_resize_f32, csrc/resize.hip): coordinates and weights in float64, the result not
+    clamped.  Exactly one of size and scale_factor (see resize_geometry).  out: an optional preallocated float32 [n,c,ho,wo] tensor
+    on the same device.  Asynchronous on the current stream; with antialias a float32 [n,c,h,wo] intermediate is allocated."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise CtHipError("bicubic_resize needs a [n,c,h,w] tensor")
+    (ho, wo), (sh, sw) = resize_geometry((x.shape[2], x.shape[3]), size=size, scale_factor=scale_factor)
+    _require_cuda(x)
+    if x.dtype != torch.float32:
+        raise CtHipError("bicubic_resize needs a float32 tensor (got %s)" % x.dtype)
+    n, c, h, w = x.shape
+    shape = (n, c, ho, wo)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != x.device or tuple(out.shape) != shape:
+            raise CtHipError("bicubic_resize: out must be a float32 %s tensor on %s" % (list(shape), x.device))
+        _require_cuda(out)
+    if n * c:
+        tmp = torch.empty((n * c, h, wo), dtype=torch.float32, device=x.device) if antialias else None
+        check(lib().ct_bicubic_resize_f32(_ptr(x), _ptr(out), n * c, h, w, ho, wo, sh, sw, 1 if antialias else 0,
+                                          _ptr(tmp) if antialias else None, tmp.numel() * 4 if antialias else 0, _stream()))
     return out
 
 

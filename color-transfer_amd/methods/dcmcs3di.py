@@ -10,6 +10,8 @@ ct_hip.pam_streaming (ct_pam_attend_f32 / ct_pam_valid_f32 when the [B,H,W,W] ma
 only allocates tensors.  Training (`step`, losses, logging: dcmcs3di.py:68-147) is out of scope.
 `disparity(left, right)` gives the left view's disparity of the reference's log_images (dcmcs3di.py:126,
 pasmnet/utils.py:55-105) from the streaming attention, at any width and without a [B,H,W,W] map.
+`forward_scaled(left, right, scale_factor)` is the calling convention of the reference's demo notebook (cell 24): bicubic down, the
+forward at the reduced size, bicubic back up (ct_hip.bicubic_resize).
 No CPU fallback.
 """
 import torch
@@ -168,3 +170,22 @@ class DCMCS3DI(torch.nn.Module):
                 if want_att else (None, None)
             valid = (valid_left, p["valid_right"] > 0.5)
         return p["corrected"], ((p["att_r2l"], p["att_l2r"]), att_cycle, valid, p["warped_rgb"])
+
+    @torch.no_grad()
+    def forward_scaled(self, left, right, scale_factor=0.75, antialias=False):
+        """Inference at a reduced size, as the reference's demo notebook runs this model (cell 24):
+            target, reference = F.interpolate(., scale_factor=scale_factor, mode="bicubic")      both views, ONE launch
+            result, _ = model(target, reference, inference=True)                                  the streaming path
+            result = F.interpolate(result, size=(H, W), mode="bicubic")
+        Returns (corrected_full [B,3,H,W] float32, valid_left_lowres [B,1,h,w] bool).  corrected_full is NOT clamped: the bicubic
+        kernel overshoots [0, 1], and the notebook leaves that to whoever writes the frame.  antialias is F.interpolate's flag, for
+        both resamplings (the notebook does not set it).  Bitwise what the public pieces give when called one after the other."""
+        if not left.is_cuda:
+            raise ct_hip.CtHipError("DCMCS3DI runs on the GPU only (no CPU fallback)")
+        if left.dim() != 4 or left.shape != right.shape:
+            raise ValueError("forward_scaled needs two [B,3,H,W] views of one shape")
+        B, H, W = left.shape[0], left.shape[2], left.shape[3]
+        both = torch.cat([left.float(), right.float()], dim=0)             # [2B,3,H,W]: one resize launch for the two views
+        low = ct_hip.bicubic_resize(both, scale_factor=scale_factor, antialias=antialias)
+        corrected, (_, _, (valid_left, _), _) = self.forward(low[:B], low[B:], inference=True)
+        return ct_hip.bicubic_resize(corrected, size=(H, W), antialias=antialias), valid_left

@@ -1,5 +1,6 @@
 """`python -m utils.cli test --config <yaml> [--model.func_spec ...] [--data.n_frames N] [--ckpt_path P]`
 `python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--writer.depth D] [--writer.workers N] [...]`
+both with `[--inference.scale_factor S] [--inference.antialias B]`
 
 A minimal look-alike of the reference's LightningCLI entry point (utils/cli.py:1-3, README.md:69-71) for the
 `test` and `predict` sub-commands (Lightning/jsonargparse are not part of this stack): YAML with `class_path/init_args`
@@ -12,6 +13,10 @@ with ONE collective (utils/sharding.py); rank 0 prints their means.
 `predict`: the corrected frames themselves, as bytes -- rint(clamp(x, 0, 1) * 255) on the device (ct_hip.pack_u8, the reference's
 img_as_ubyte(x.clip(0, 1)), utils/postprocess.py:138-144), downloaded through a ring of pinned buffers and written by frame index
 (utils/writer.py): every rank writes its own frames into the one directory, the result does not depend on the world size.
+
+`inference` (optional section, `inference: {scale_factor: 0.75, antialias: false}` or `--inference.scale_factor 0.75`): the model runs
+at a reduced size through its `forward_scaled` -- bicubic down, forward, bicubic back up, the reference's demo notebook, cell 24 -- and
+metrics / frames are those of the full-size result.  A model without `forward_scaled` is refused.  Without the section nothing changes.
 """
 import importlib
 import os
@@ -44,6 +49,22 @@ def _instantiate(section):
 def quantise_u8(x):
     """ct_hip.pack_u8's rule in torch, for the CT_CLI_DEVICE=cpu test mode only (torch.round is ties-to-even)"""
     return (x.clamp(0, 1).nan_to_num(0) * 255).round().to(torch.uint8)
+
+
+def _inference(cfg, model):
+    """the optional `inference` section -> None, or the keyword arguments of model.forward_scaled"""
+    sec = cfg.get("inference")
+    if not sec:
+        return None
+    if not isinstance(sec, dict) or set(sec) - {"scale_factor", "antialias"} or "scale_factor" not in sec:
+        raise SystemExit("the `inference` section takes `scale_factor` (required) and `antialias`; got %r" % (sec,))
+    sf, aa = sec["scale_factor"], sec.get("antialias", False)
+    if isinstance(sf, bool) or not isinstance(sf, (int, float)) or not 0 < sf < float("inf") or not isinstance(aa, bool):
+        raise SystemExit("inference.scale_factor must be a positive number and inference.antialias true or false; got %r" % (sec,))
+    if not hasattr(model, "forward_scaled"):
+        raise SystemExit("the `inference` section (reduced-scale inference) needs a model with `forward_scaled`; %s has none "
+                         "(methods.dcmcs3di.DCMCS3DI does)" % type(model).__name__)
+    return {"scale_factor": float(sf), "antialias": aa}
 
 
 def _parse(argv):
@@ -89,6 +110,7 @@ def _setup(cfg, ckpt):
     if world > 1 and dist.get_world_size() != world:
         raise SystemExit("WORLD_SIZE=%d but the process group has %d ranks" % (world, dist.get_world_size()))
     model = _instantiate(cfg["model"]).to(device).eval()
+    scaled = _inference(cfg, model)
     if ckpt:
         # Lightning checkpoints carry hyper-parameters / optimizer state next to "state_dict"; weights_only=True refuses the
         # ones that pickle arbitrary objects.  Falling back to the unsafe loader executes whatever the file pickles, so it
@@ -115,7 +137,7 @@ def _setup(cfg, ckpt):
             torch.cuda.synchronize()
 
     return types.SimpleNamespace(rank=rank, world=world, on_cpu=on_cpu, device=device, own_group=own_group, model=model,
-                                 loaders=loaders, fence=fence)
+                                 loaders=loaders, fence=fence, scaled=scaled)
 
 
 def main(argv=None, timing=None):
@@ -156,7 +178,7 @@ def _test(ctx, timing):
     tables = []
     for li, frames in enumerate(loaders):
         mine = sh.frames_of_rank(len(frames), rank, world)
-        grouped = (not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "test_group") and model.takes_groups())
+        grouped = (not ctx.scaled and not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "test_group") and model.takes_groups())
         if grouped:
             # uint8 frames in pinned groups (configs[4]): one upload and ONE fused call per group -- transfer + clamp + PSNR of
             # Runner.test_step (methods/__init__.py:29-32) -- no torch kernel in the loop, one gather at the end
@@ -186,7 +208,10 @@ def _test(ctx, timing):
             rows = []
             for f, sample in prefetch(frames, mine, device):       # pinned double-buffered uploads on a second stream
                 batch = {k: v.unsqueeze(0) for k, v in sample.items()}
-                if hasattr(model, "test_step"):
+                if ctx.scaled:                          # reduced-scale inference, scored at full size like the branch below
+                    corrected = model.forward_scaled(batch["target"], batch["reference"], **ctx.scaled)[0].clamp(0, 1)
+                    rows.append(torch.stack([fn(corrected, batch["gt"]).reshape(()) for fn in (psnr, ssim, fsim, icid)]))
+                elif hasattr(model, "test_step"):
                     m = model.test_step(batch, f)
                     nan = torch.full((), float("nan"), device=device)
                     rows.append(torch.stack([m[k].reshape(()).to(device) if k in m else nan for k in METRICS]))
@@ -230,7 +255,7 @@ def _predict(ctx, output, fmt, writer_cfg, timing):
     for li, frames in enumerate(loaders):
         out_dir = os.path.join(output, "idx_%d" % li) if len(loaders) > 1 else output
         mine = sh.frames_of_rank(len(frames), rank, world)
-        grouped = (not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "predict_group") and model.takes_groups())
+        grouped = (not ctx.scaled and not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "predict_group") and model.takes_groups())
         if rank == 0:
             os.makedirs(out_dir, exist_ok=True)
             if fmt == "raw":
@@ -259,7 +284,9 @@ def _predict(ctx, output, fmt, writer_cfg, timing):
                     return
                 for n, (f, sample) in enumerate(prefetch(frames, indices, device)):
                     batch = {k: v.unsqueeze(0) for k, v in sample.items()}
-                    if hasattr(model, "test_step"):             # the Runner interface: what test_step scores (methods/__init__.py:30)
+                    if ctx.scaled:                              # reduced-scale inference: the full-size frame, clamped by the pack
+                        corrected = model.forward_scaled(batch["target"], batch["reference"], **ctx.scaled)[0]
+                    elif hasattr(model, "test_step"):           # the Runner interface: what test_step scores (methods/__init__.py:30)
                         corrected = model(batch).clamp(0, 1)
                     else:                                       # CNN modules: forward(target, reference, inference=True)
                         corrected = model(batch["target"], batch["reference"], inference=True)[0]

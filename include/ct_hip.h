@@ -221,6 +221,25 @@ int ct_distort_u8(const uint8_t *in, int height, int width, int kind, double par
 #define CT_PACK_CHW 1
 int ct_pack_u8_f32(const float *in, int layout, int n, int height, int width, uint8_t *out_hwc, void *stream);
 
+/* ---- bicubic resampling (the reference's demo notebook, cell 24: F.interpolate(x, scale_factor=0.75, mode="bicubic") around
+ * DCMCS3DI and F.interpolate(result, size=(H, W), mode="bicubic") after it; csrc/resize.hip) -------------------------------
+ * in: float32 [planes][h][w] (NCHW with planes = n * c), out: float32 [planes][ho][wo]; element offsets are 64-bit.
+ * torch.nn.functional.interpolate(mode="bicubic", align_corners=False) of torch 2.10: cubic convolution with A = -0.75 on the
+ * taps floor(s) - 1 .. floor(s) + 2 clamped to the border, s = scale * (o + 0.5) - 0.5; the result is not clamped.
+ * scale_h / scale_w: the source step per output pixel as torch derives it -- 1 / scale_factor when the caller gave a factor,
+ * in / out when it gave a size -- in double: coordinates and weights are evaluated in float64 (torch's float32 kernel rounds s
+ * to float32), and without antialias the 16 taps are accumulated in float64 and rounded once.
+ * antialias != 0: F.interpolate(..., antialias=True) -- separable, columns then rows, filter support 2 * max(scale, 1), taps cut
+ * at the border, A = -0.5, weights normalised per output pixel; float32 intermediate [planes][h][wo] in ws
+ * (ct_bicubic_resize_workspace_bytes; 0 without antialias, ws may be NULL then).  A reduction beyond 31-fold on an axis (more than
+ * 128 taps) is CT_E_BADARG with antialias.
+ * wo % 4 == 0 and a 16-byte aligned out take 16-byte stores, anything else an element-wise path of the same rule.
+ * A null pointer, a size < 1 or a scale that is not in (0, 1e9]: CT_E_BADARG; in / out not aligned to 4 bytes: CT_E_ALIGN; ws
+ * missing, misaligned or too small with antialias: CT_E_WORKSPACE.  Deterministic.  Added under ABI 9.                          */
+size_t ct_bicubic_resize_workspace_bytes(int64_t planes, int h, int wo, int antialias);
+int ct_bicubic_resize_f32(const float *in, float *out, int64_t planes, int h, int w, int ho, int wo, double scale_h,
+                          double scale_w, int antialias, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- per-frame metric (first step): PSNR as Runner.test_step logs it (methods/__init__.py:32,37) ----
  * a, b: [batch][n_elems] float32 (any layout, same for both); out[i] = {mse, 10 log10(1/mse)} (data range 1).
  * Deterministic float64 reduction.  ws: batch * 1024 doubles (ct_workspace_bytes(CT_WS_LAB_STATS, ., batch) suffices). */
