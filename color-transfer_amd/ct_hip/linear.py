@@ -1,0 +1,246 @@
+"""Reinhard / MK / Xiao: Lab and RGB statistics, the affine maps, the fused and persistent Reinhard entries, the Lab mode."""
+import ctypes
+
+import torch
+
+from ._core import (CT_LAB_STATS_STRIDE, CT_RGB_STATS_STRIDE, CT_WS_LAB_STATS, CT_WS_REINHARD, CT_WS_REINHARD_PERSIST,
+                    CT_WS_REINHARD_PSNR, CT_WS_RGB_MEANCOV, CtHipError, SIGNATURES, _as_batch, _c_i64, _c_int, _c_p,
+                    _c_sz, _ptr, _require_cuda, _stream, _suffix, check, lib, workspace)
+
+SIGNATURES.update({
+    "ct_profile_events": (None, [_c_p, _c_p, _c_p, _c_p]),
+    "ct_set_lab_mode": (_c_int, [_c_int]),
+    "ct_get_lab_mode": (_c_int, []),
+    "ct_set_lab_mode_thread": (_c_int, [_c_int]),
+    "ct_lab_stats_f32": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_lab_stats_f64": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_reinhard_apply_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_reinhard_apply_f64": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_reinhard_lab_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_reinhard_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_reinhard_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_reinhard_psnr_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_reinhard_persist_supported": (_c_int, [_c_i64]),
+    "ct_reinhard_takes_persist": (_c_int, [_c_i64]),
+    "ct_reinhard_persist_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_reinhard_psnr_u8": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_rgb_meancov_f32": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_rgb_meancov_f64": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_mk_f32_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_sz, _c_p]),
+    "ct_mk_f32_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_sz, _c_p]),
+    "ct_mk_f64_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_sz, _c_p]),
+    "ct_mk_coef_f64": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_p, _c_p]),
+    "ct_affine3x3_f32_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_affine3x3_f64_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_affine3x3_f32_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+})
+
+CT_LAB_TABLE, CT_LAB_EXACT = 0, 1
+
+
+def set_lab_mode(mode, thread=False):
+    """Lab arithmetic of the float32 Reinhard entries: "table" (default; LDS look-up tables, Lab within ~5e-7 of the
+    float64 path) or "exact" (float64 with hardware seeds).  Process-wide default (ct_set_lab_mode), or -- thread=True -- an
+    override for the calling thread only (ct_set_lab_mode_thread; mode None removes it)."""
+    if thread and mode is None:
+        check(lib().ct_set_lab_mode_thread(-1))
+        return
+    code = {"table": CT_LAB_TABLE, "exact": CT_LAB_EXACT}.get(mode)
+    if code is None:
+        raise ValueError("lab mode must be 'table' or 'exact', got %r" % (mode,))
+    check(lib().ct_set_lab_mode_thread(code) if thread else lib().ct_set_lab_mode(code))
+
+
+def lab_mode():
+    return "exact" if lib().ct_get_lab_mode() == CT_LAB_EXACT else "table"
+
+
+def profile_events(events):
+    """events: None (off) or four torch.cuda.Event(enable_timing=True) that have been recorded once (so that their
+    hipEvent_t exists); the library re-records them around moments_kernel / reinhard_apply_kernel."""
+    if events is None:
+        lib().ct_profile_events(None, None, None, None)
+    else:
+        lib().ct_profile_events(*[ctypes.c_void_p(e.cuda_event) for e in events])
+
+
+def lab_stats(img):
+    """rgb2lab + mean/std (population) per image: returns float64 [B, 8] = mean[3], std[3], n, 0.
+    Replaces methods/linear.py:25-26,33-36."""
+    x, _ = _as_batch(img)
+    _require_cuda(x)
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    stats = torch.empty((B, CT_LAB_STATS_STRIDE), dtype=torch.float64, device=x.device)
+    ws = workspace(CT_WS_LAB_STATS, n, B, x.device)
+    fn = getattr(lib(), "ct_lab_stats_" + _suffix(x))
+    check(fn(_ptr(x), n, B, _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    return stats
+
+
+def rgb_meancov(img):
+    """np.mean + np.cov (ddof 1) per image: float64 [B, 16] = mean[3], cov[9], n, 0,0,0.
+    Replaces methods/linear.py:64-67,103-106."""
+    x, _ = _as_batch(img)
+    _require_cuda(x)
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    stats = torch.empty((B, CT_RGB_STATS_STRIDE), dtype=torch.float64, device=x.device)
+    ws = workspace(CT_WS_RGB_MEANCOV, n, B, x.device)
+    fn = getattr(lib(), "ct_rgb_meancov_" + _suffix(x))
+    check(fn(_ptr(x), n, B, _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    return stats
+
+
+def reinhard_apply(target, stats_t, stats_r, out=None, to_lab=False):
+    """Affine map in Lab + lab2rgb (methods/linear.py:38-40); stats stay on the device."""
+    x, _ = _as_batch(target)
+    _require_cuda(x, stats_t, stats_r)
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    if out is None:
+        out = torch.empty_like(x)
+    if to_lab:
+        if x.dtype != torch.float32:
+            raise CtHipError("the Lab probe exists for float32 only")
+        fn = lib().ct_reinhard_lab_f32
+    else:
+        fn = getattr(lib(), "ct_reinhard_apply_" + _suffix(x))
+    check(fn(_ptr(x), _ptr(stats_t), _ptr(stats_r), _ptr(out), n, B, _stream()))
+    return out.view(target.shape)
+
+
+def reinhard(target, reference, out=None, stats_out=None):
+    """methods.linear.color_transfer_between_images on device tensors, B pairs per call
+    (same H x W for target and reference).  One stats sweep over all 2B images, a finishing
+    kernel, one apply sweep; no host synchronisation."""
+    x, _ = _as_batch(target)
+    r, _ = _as_batch(reference)
+    _require_cuda(x, r)
+    if x.shape != r.shape or x.dtype != r.dtype:
+        raise CtHipError("fused reinhard needs equal shapes/dtypes; use lab_stats + reinhard_apply otherwise")
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    if out is None:
+        out = torch.empty_like(x)
+    ws = workspace(CT_WS_REINHARD, n, B, x.device)
+    fn = getattr(lib(), "ct_reinhard_" + _suffix(x))
+    if stats_out is not None:
+        _require_cuda(stats_out)
+        if stats_out.dtype != torch.float64 or stats_out.numel() < 2 * B * CT_LAB_STATS_STRIDE:
+            raise CtHipError("stats_out must be float64 with >= 2*B*8 elements")
+    sp = _ptr(stats_out) if stats_out is not None else ctypes.c_void_p(0)
+    check(fn(_ptr(x), _ptr(r), _ptr(out), n, B, sp, _ptr(ws), ws.numel(), _stream()))
+    return out.view(target.shape)
+
+
+def reinhard_psnr(target, reference, gt, out=None, psnr_out=None):
+    """color_transfer_between_images for B float32 pairs + the per-frame PSNR of the result against `gt` (same layout as the
+    images), as Runner.test_step computes it (methods/__init__.py:30-32).  Returns (out, psnr float64 [B, 2] = mse, PSNR)."""
+    x, _ = _as_batch(target)
+    r, _ = _as_batch(reference)
+    g, _ = _as_batch(gt)
+    _require_cuda(x, r, g)
+    if not (x.shape == r.shape == g.shape) or not (x.dtype == r.dtype == g.dtype == torch.float32):
+        raise CtHipError("reinhard_psnr needs three float32 tensors of one shape")
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    if out is None:
+        out = torch.empty_like(x)
+    if psnr_out is None:
+        psnr_out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    ws = workspace(CT_WS_REINHARD_PSNR, n, B, x.device)
+    check(lib().ct_reinhard_psnr_f32(_ptr(x), _ptr(r), _ptr(g), _ptr(out), _ptr(psnr_out), n, B, ctypes.c_void_p(0), _ptr(ws), ws.numel(),
+                                     _stream()))
+    return out.view(target.shape), psnr_out
+
+
+def reinhard_persist_supported(n_pixels):
+    """True when frames of n_pixels can take the one-launch Reinhard kernel on this device (csrc/reinhard_persist.hip)."""
+    return bool(lib().ct_reinhard_persist_supported(int(n_pixels)))
+
+
+def reinhard_takes_persist(n_pixels):
+    """True when reinhard() / reinhard_psnr() run float32 frames of n_pixels as the persistent launch (current Lab mode)."""
+    return bool(lib().ct_reinhard_takes_persist(int(n_pixels)))
+
+
+def reinhard_persist(target, reference, gt=None, out=None, psnr_out=None, stats_out=None, verify=False):
+    """color_transfer_between_images (methods/linear.py:8-42) for B pairs as ONE persistent launch, optionally with the
+    per-frame PSNR against `gt`.  float32 frames in [0,1] or uint8 frames (the reference's `.float() / 255`, utils/data.py:84);
+    the result is float32.  Returns out, or (out, psnr [B, 2]) with gt.  verify=True synchronises and raises if a workgroup of
+    the grid never became resident (results NaN)."""
+    x, _ = _as_batch(target)
+    r, _ = _as_batch(reference)
+    ts = [x, r]
+    g = None
+    if gt is not None:
+        g, _ = _as_batch(gt)
+        ts.append(g)
+    _require_cuda(*ts)
+    if any(t.shape != x.shape or t.dtype != x.dtype for t in ts) or x.dtype not in (torch.float32, torch.uint8):
+        raise CtHipError("reinhard_persist needs float32 or uint8 tensors of one shape")
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    if not reinhard_persist_supported(n):
+        raise CtHipError("frames of %d pixels do not fit the persistent Reinhard launch on this device" % n)
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if g is not None and psnr_out is None:
+        psnr_out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    if stats_out is not None:
+        _require_cuda(stats_out)
+        if stats_out.dtype != torch.float64 or stats_out.numel() < 2 * B * CT_LAB_STATS_STRIDE:
+            raise CtHipError("stats_out must be float64 with >= 2*B*8 elements")
+    ws = workspace(CT_WS_REINHARD_PERSIST, n, B, x.device)
+    null = ctypes.c_void_p(0)
+    if x.dtype == torch.uint8:
+        fn = lib().ct_reinhard_psnr_u8
+    else:
+        fn = lib().ct_reinhard_persist_f32
+    check(fn(_ptr(x), _ptr(r), _ptr(g) if g is not None else null, _ptr(out), _ptr(psnr_out) if g is not None else null, n, B,
+                          _ptr(stats_out) if stats_out is not None else null, _ptr(ws), ws.numel(), _stream()))
+    if verify:
+        torch.cuda.synchronize()
+        if int(ws[:4].view(torch.int32)[0].item()) != 0:
+            raise CtHipError("persistent Reinhard launch: a workgroup of the grid never became resident (results are NaN)")
+    o = out.view(tuple(target.shape))
+    return (o, psnr_out) if g is not None else o
+
+
+def mk(target, reference, decomposition="MK", out_dtype=torch.float64, out=None):
+    """methods.linear.monge_kantorovitch_color_transfer on device tensors, B pairs per call, no host sync (ct_mk_*)."""
+    x, _ = _as_batch(target)
+    r, _ = _as_batch(reference)
+    _require_cuda(x, r)
+    if x.shape != r.shape or x.dtype != r.dtype:
+        raise CtHipError("fused mk needs equal shapes/dtypes")
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    name = "ct_mk_%s_%s" % (_suffix(x), _suffix(out))
+    if name not in SIGNATURES:
+        raise CtHipError("no kernel for %s" % name)
+    ws = workspace(CT_WS_REINHARD, n, B, x.device)
+    mode = {"MK": 0, "sqrt": 1, "cholesky": 2}[decomposition]
+    check(getattr(lib(), name)(_ptr(x), _ptr(r), _ptr(out), n, B, mode, _ptr(ws), ws.numel(), _stream()))
+    return out.view(target.shape)
+
+
+def mk_coef(stats_t, stats_r, decomposition="MK"):
+    """On-device 3x3 algebra of MK (methods/linear.py:108-118): rgb_meancov records -> affine3x3 coefficient records."""
+    mode = {"MK": 0, "sqrt": 1, "cholesky": 2}[decomposition]
+    _require_cuda(stats_t, stats_r)
+    b = stats_t.shape[0]
+    coef = torch.empty((b, 16), dtype=torch.float64, device=stats_t.device)
+    check(lib().ct_mk_coef_f64(_ptr(stats_t), _ptr(stats_r), mode, b, _ptr(coef), _stream()))
+    return coef
+
+
+def affine3x3(img, coef, out_dtype=torch.float64, out=None):
+    """out = (x - mu_t) @ A + mu_r per image; coef float64 [B,16] = A[9], mu_t[3], mu_r[3], 0.
+    Replaces methods/linear.py:80,122."""
+    x, _ = _as_batch(img)
+    _require_cuda(x, coef)
+    B, n = x.shape[0], x.shape[1] * x.shape[2]
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    name = "ct_affine3x3_%s_%s" % (_suffix(x), _suffix(out))
+    if name not in SIGNATURES:
+        raise CtHipError("no kernel for %s" % name)
+    check(getattr(lib(), name)(_ptr(x), _ptr(coef), _ptr(out), n, B, _stream()))
+    return out.view(img.shape)

@@ -194,6 +194,32 @@ def test_fp16_piece_packings_layout_and_value():
             got = v[idx].sum()
             assert abs(got - want) <= 2.0 ** -21 * abs(want) + 2.0 ** -24
         assert v[(cout + 63) // 64 - 1, :, :, :, 1, :, (cout % 32 or 32):].abs().sum() == 0 or cout % 64 == 0 or cout % 64 > 32
+    # the whole packed images, bit for bit, against the packing spelled out: w_exp puts the largest magnitude into [2^11, 2^12)
+    # (clamped to +-100), hi = fp16(w 2^w_exp), lo = fp16(w 2^w_exp - hi), both as int16 bit patterns
+    def hi_lo(w):
+        amax = float(w.abs().max())
+        w_exp = 0 if not (amax > 0 and amax < float("inf")) else 12 - (int(np.floor(np.log2(amax))) + 1)
+        w_exp = max(-100, min(100, w_exp))
+        ws = w * (2.0 ** w_exp)
+        hi = ws.to(torch.float16)
+        lo = (ws - hi.float()).to(torch.float16)
+        return torch.stack([hi, lo], dim=0).view(torch.int16), w_exp
+    for (cout, cin, scale) in ((70, 40, 0.05), (64, 64, 3e-7)):
+        weight = torch.randn(cout, cin, 3, 3, generator=g) * scale
+        grp, nc = (cout + 63) // 64, (cin + 15) // 16
+        w = torch.zeros((grp * 64, nc * 16, 3, 3), dtype=torch.float32)
+        w[:cout, :cin] = weight
+        pieces, w_exp = hi_lo(w)
+        want = pieces.reshape(2, grp, 2, 32, nc, 2, 8, 9).permute(1, 4, 7, 0, 2, 5, 3, 6).contiguous()
+        img, got_exp = ct_hip.pack_conv_weight_split16(weight)
+        assert got_exp == w_exp and img.dtype == torch.int16 and torch.equal(img, want)
+        w = torch.zeros((grp * 64, 64, 3, 3), dtype=torch.float64)
+        w[:cout, :cin] = weight.double()
+        G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
+        pieces, w_exp = hi_lo(torch.einsum("ij,kcjl,ml->kcim", G, w, G).float())
+        want = pieces.reshape(2, grp, 4, 16, 2, 4, 8, 16).permute(1, 7, 2, 4, 0, 5, 3, 6).contiguous().reshape(grp, 16, 4, 2, 2, 64, 8)
+        img, got_exp = ct_hip.pack_conv_weight_wino16(weight)
+        assert got_exp == w_exp and img.dtype == torch.int16 and torch.equal(img, want)
 
 
 def test_winograd_weight_packing_layout_and_value():
