@@ -43,6 +43,39 @@ def fsim(x, y):
     return ct_hip.frame_fsim(x.float().contiguous(), y.float().contiguous())
 
 
+GT_VIEWS = ("chess", "rgbmse")          # the views that compare with the ground truth
+
+
+def select_views(offered, names, have_gt):
+    """The `names` argument of a model's views(): None = every offered view (without a ground truth: those that need none), a
+    comma-separated string or a sequence.  Unknown names, and a view that needs gt without one, raise ValueError."""
+    if names is None:
+        return tuple(v for v in offered if have_gt or v not in GT_VIEWS)
+    names = tuple(n.strip() for n in names.split(",")) if isinstance(names, str) else tuple(names)
+    bad = [n for n in names if n not in offered]
+    if bad:
+        raise ValueError("unknown view%s %s: this model offers %s" % ("s" if len(bad) > 1 else "", ", ".join(map(repr, bad)), ", ".join(offered)))
+    if not have_gt and any(n in GT_VIEWS for n in names):
+        raise ValueError("the views %s compare with the ground truth: pass gt" % " and ".join(n for n in names if n in GT_VIEWS))
+    return names
+
+
+def gt_views(view, corrected, gt):
+    """`corrected`, `chess` or `rgbmse` of float32 [B,3,H,W] device tensors as uint8 [B,H,W,3], the panel of the reference's
+    log_images (methods/dcmcs3di.py:131-135): pack_u8 of the frame, of chess_mix(gt, corrected), of rgbmse(gt, corrected)"""
+    import ct_hip
+    if view == "corrected":
+        return ct_hip.pack_u8(corrected, "chw")
+    fn = ct_hip.chess_mix if view == "chess" else ct_hip.rgbmse_view
+    return ct_hip.pack_u8(fn(gt, corrected), "chw")
+
+
+def mask_view(mask):
+    """a 0/1 float mask [B,1,H,W] -> uint8 [B,H,W,3], 255 where it is set"""
+    import ct_hip
+    return ct_hip.pack_u8(mask.expand(-1, 3, -1, -1).contiguous(), "chw")
+
+
 METRICS = ("Test PSNR", "Test SSIM", "Test FSIM", "Test iCID")        # what test_step logs, in its order (methods/__init__.py:37-40)
 
 
@@ -105,6 +138,21 @@ class Runner(torch.nn.Module):
             r = r.permute(1, 2, 0).detach().cpu().numpy()
             outputs.append(torch.from_numpy(self.func(t, r)).float().permute(2, 0, 1))
         return torch.stack(outputs).to(target.device)
+
+    VIEWS = ("corrected", "chess", "rgbmse")
+
+    @torch.no_grad()
+    def views(self, batch, names=None):
+        """Diagnostic images of one batch as an ordered dict of uint8 [B,H,W,3] device tensors: `corrected` =
+        pack_u8(forward(batch).clamp(0, 1)), and with batch["gt"] `chess` = pack_u8(chess_mix(gt, corrected)) and `rgbmse` =
+        pack_u8(rgbmse_view(gt, corrected)).  One forward serves every view; each is bitwise what those public calls give one after
+        the other.  names: a subset (sequence or comma-separated string).  GPU only."""
+        gt = batch.get("gt")
+        names = select_views(self.VIEWS, names, gt is not None)
+        corrected = self(batch).clamp(0, 1).float().contiguous()
+        if gt is not None:
+            gt = gt.to(corrected.device).float().contiguous()
+        return {n: gt_views(n, corrected, gt) for n in names}
 
     def test_step(self, batch, batch_idx=0, dataloader_idx=0):
         result = self(batch).clamp(0, 1)

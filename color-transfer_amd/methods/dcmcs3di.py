@@ -12,6 +12,7 @@ only allocates tensors.  Training (`step`, losses, logging: dcmcs3di.py:68-147) 
 pasmnet/utils.py:55-105) from the streaming attention, at any width and without a [B,H,W,W] map.
 `forward_scaled(left, right, scale_factor)` is the calling convention of the reference's demo notebook (cell 24): bicubic down, the
 forward at the reduced size, bicubic back up (ct_hip.bicubic_resize).
+`views(left, right, gt)` gives the image panel of the reference's log_images (dcmcs3di.py:116-144) as uint8 frames on the device.
 No CPU fallback.
 """
 import torch
@@ -33,6 +34,8 @@ def sequential_forward(seq, x):
 
 
 class DCMCS3DI(torch.nn.Module):
+    VIEWS = ("corrected", "chess", "rgbmse", "disparity", "warped_right", "occlusions")
+
     def __init__(self, extraction_layers=18, transfer_layers=6, channels=64):
         super().__init__()
         self.hparams = type("HParams", (), dict(extraction_layers=extraction_layers, transfer_layers=transfer_layers,
@@ -170,6 +173,37 @@ class DCMCS3DI(torch.nn.Module):
                 if want_att else (None, None)
             valid = (valid_left, p["valid_right"] > 0.5)
         return p["corrected"], ((p["att_r2l"], p["att_l2r"]), att_cycle, valid, p["warped_rgb"])
+
+    @torch.no_grad()
+    def views(self, left, right, gt=None, names=None):
+        """The image panel of the reference's log_images (dcmcs3di.py:116-144) at inference, as an ordered dict of uint8 [B,H,W,3]
+        device tensors (what utils.writer.FrameWriter takes):
+            corrected     pack_u8 of the corrected left view
+            chess         pack_u8(chess_mix(gt, corrected))                      needs gt
+            rgbmse        pack_u8(rgbmse_view(gt, corrected))                    needs gt
+            disparity     pack_u8(gray_view(disp_left)), forward_parts(want_disp=True)'s filled disparity, min-max scaled per frame
+            warped_right  pack_u8(warped_rgb), the right view under the parallax attention
+            occlusions    255 where valid_left is false
+        names: a subset (sequence or comma-separated string; default: all, without gt those that need none).  Unknown names and
+        a gt view without gt raise ValueError.  ONE forward serves every view, and each is bitwise what the public pieces named
+        above give when called one after the other."""
+        from methods import gt_views, mask_view, select_views
+        names = select_views(self.VIEWS, names, gt is not None)
+        p = self.forward_parts(left, right, want_disp="disparity" in names)
+        corrected = p["corrected"]
+        if gt is not None:
+            gt = gt.to(corrected.device).float().contiguous()
+        out = {}
+        for n in names:
+            if n == "disparity":
+                out[n] = ct_hip.pack_u8(ct_hip.gray_view(p["disp_left"]), "chw")
+            elif n == "warped_right":
+                out[n] = ct_hip.pack_u8(p["warped_rgb"].contiguous(), "chw")
+            elif n == "occlusions":
+                out[n] = mask_view((~(p["valid_left"] > 0.5)).float())
+            else:
+                out[n] = gt_views(n, corrected, gt)
+        return out
 
     @torch.no_grad()
     def forward_scaled(self, left, right, scale_factor=0.75, antialias=False):

@@ -24,6 +24,8 @@ from unimatch import GMFlow
 
 
 class DMSCT(torch.nn.Module):
+    VIEWS = ("corrected", "chess", "rgbmse", "flow", "warped_right", "occlusions")
+
     def __init__(self, encoder_name="efficientnet-b2", encoder_depth=4, encoder_weights=None,
                  decoder_channels=(256, 128, 64, 32), encoder=None, decoder=None, head=None, matcher_weights=None):
         super().__init__()
@@ -84,7 +86,10 @@ class DMSCT(torch.nn.Module):
         return out
 
     def forward(self, target, reference):
-        m = self.match(target, reference)
+        return self._forward(target, reference, self.match(target, reference))
+
+    def _forward(self, target, reference, m):
+        """the forward pass given the matcher's result m"""
         _, _, height, width = reference.shape
         pad_size = self.derive_pad_size(reference.shape)
         pad = torch.nn.functional.pad
@@ -99,6 +104,36 @@ class DMSCT(torch.nn.Module):
             fr = self.encoder(pad(reference, pad_size, mode="replicate"))
         features = self.fuse_features(m["flow"], m["fwd_occ"], ft, fr, pad_size)
         return torch.clamp(target + self.head(self.decoder(*features))[:, :, :height, :width], min=0, max=1)
+
+    @torch.no_grad()
+    def views(self, target, reference, gt=None, names=None):
+        """The image panel of the reference's log_images (dmsct.py:148-184) as an ordered dict of uint8 [B,H,W,3] device tensors:
+            corrected     pack_u8(forward(target, reference))
+            chess         pack_u8(chess_mix(gt, corrected))                      needs gt
+            rgbmse        pack_u8(rgbmse_view(gt, corrected))                    needs gt
+            flow          flow_to_image(match["flow"]), the Middlebury colour code, each frame scaled by its own largest flow
+            warped_right  pack_u8(flow_warp(reference, match["flow"]))
+            occlusions    255 * match["fwd_occ"]
+        ONE match and one forward serve every view: the flow shown is the flow of `match`, computed at the reduced
+        derive_matcher_inference_size -- the one the correction actually used.  (The reference's logging call runs the matcher a
+        second time, at full size, for its panel.)  names, errors and the bitwise rule as for DCMCS3DI.views."""
+        from methods import gt_views, mask_view, select_views
+        names = select_views(self.VIEWS, names, gt is not None)
+        m = self.match(target, reference)
+        corrected = self._forward(target, reference, m).float().contiguous()
+        if gt is not None:
+            gt = gt.to(corrected.device).float().contiguous()
+        out = {}
+        for n in names:
+            if n == "flow":
+                out[n] = ct_hip.flow_to_image(m["flow"].contiguous())
+            elif n == "warped_right":
+                out[n] = ct_hip.pack_u8(ct_hip.flow_warp(reference.float().contiguous(), m["flow"].contiguous()), "chw")
+            elif n == "occlusions":
+                out[n] = mask_view(m["fwd_occ"])
+            else:
+                out[n] = gt_views(n, corrected, gt)
+        return out
 
     @torch.no_grad()
     def test_step(self, batch, batch_idx=0, dataloader_idx=0):

@@ -451,7 +451,8 @@ class GMFlow(nn.Module):
                 corr_radius_list=(-1, 4), prop_radius_list=(-1, 1), num_reg_refine=6, pred_bidir_flow=False,
                 pred_bwd_flow=False, pred_flow_viz=False, fwd_bwd_consistency_check=False, dbg=None, **kwargs):
         """unimatch/__init__.py:60-167 with the default split / radius lists: DMSCT's call (pred_bidir_flow=True, occlusion masks)
-        and the one-direction forms (pred_bidir_flow=False; pred_bwd_flow swaps the frames, :117-118).  No flow visualisation."""
+        and the one-direction forms (pred_bidir_flow=False; pred_bwd_flow swaps the frames, :117-118).  pred_flow_viz is refused: the
+        colour image of a flow is utils.flow_viz.flow_tensor_to_image(result["flow"][i]) (on the device, ct_hip.flow_to_image)."""
         if (pred_flow_viz or attn_type != "swin" or tuple(attn_splits_list) != (2, 8)
                 or tuple(corr_radius_list) != (-1, 4) or tuple(prop_radius_list) != (-1, 1)):
             raise NotImplementedError("GMFlow on HIP implements the default split / radius lists, without pred_flow_viz")

@@ -1,5 +1,5 @@
 """`python -m utils.cli test --config <yaml> [--model.func_spec ...] [--data.n_frames N] [--ckpt_path P]`
-`python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--writer.depth D] [--writer.workers N] [...]`
+`python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--views a,b,c] [--writer.depth D] [--writer.workers N] [...]`
 both with `[--inference.scale_factor S] [--inference.antialias B]`
 
 A minimal look-alike of the reference's LightningCLI entry point (utils/cli.py:1-3, README.md:69-71) for the
@@ -14,11 +14,17 @@ with ONE collective (utils/sharding.py); rank 0 prints their means.
 img_as_ubyte(x.clip(0, 1)), utils/postprocess.py:138-144), downloaded through a ring of pinned buffers and written by frame index
 (utils/writer.py): every rank writes its own frames into the one directory, the result does not depend on the world size.
 
+`predict --views corrected,chess,rgbmse,...`: next to every corrected frame `%06d.<ext>` the listed diagnostic views of that frame, as
+`%06d.<view>.<ext>` -- the image panel of the reference's log_images, from the model's `views()` (methods/__init__.py, methods/dcmcs3di.py,
+methods/dmsct.py), one forward per frame for all of them.  Which views exist depends on the model; one it does not offer is refused
+before the first frame.  Not with `--format raw` (one file) and not with the `inference` section.  Without `--views` nothing changes.
+
 `inference` (optional section, `inference: {scale_factor: 0.75, antialias: false}` or `--inference.scale_factor 0.75`): the model runs
 at a reduced size through its `forward_scaled` -- bicubic down, forward, bicubic back up, the reference's demo notebook, cell 24 -- and
 metrics / frames are those of the full-size result.  A model without `forward_scaled` is refused.  Without the section nothing changes.
 """
 import importlib
+import inspect
 import os
 import sys
 import types
@@ -51,6 +57,55 @@ def quantise_u8(x):
     return (x.clamp(0, 1).nan_to_num(0) * 255).round().to(torch.uint8)
 
 
+ALL_VIEWS = ("corrected", "chess", "rgbmse", "disparity", "flow", "warped_right", "occlusions")     # over all models
+CPU_VIEWS = ("corrected", "chess", "rgbmse")
+
+
+def chess_mix_cpu(x, y, size=25):
+    """ct_hip.chess_mix's rule in torch, for the CT_CLI_DEVICE=cpu test mode only"""
+    h, w = x.shape[-2:]
+    pick = (torch.arange(h)[:, None] // size + torch.arange(w)[None, :] // size) % 2 == 0
+    return torch.where(pick, x, y)
+
+
+def rgbmse_cpu(x, y):
+    """ct_hip.rgbmse_view's rule in torch (the channels added in their order, divided by 3), for the CT_CLI_DEVICE=cpu test mode only"""
+    d = x - y
+    m = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) / 3
+    lo, hi = m.amin(dim=(-1, -2), keepdim=True), m.amax(dim=(-1, -2), keepdim=True)
+    out = torch.zeros_like(x)
+    out[:, 0] = (m - lo) / (hi - lo)
+    return out
+
+
+def _view_names(value, fmt):
+    """the `--views` option -> a tuple of known view names; refused with `raw` (one file holds one image per frame)"""
+    names = tuple(n.strip() for n in str(value).split(","))
+    if not all(names):
+        raise SystemExit("--views %r: a comma-separated list of view names (%s)" % (value, ", ".join(ALL_VIEWS)))
+    bad = [n for n in names if n not in ALL_VIEWS]
+    if bad:
+        raise SystemExit("--views: unknown view %s; the views are %s" % (", ".join(map(repr, bad)), ", ".join(ALL_VIEWS)))
+    if len(set(names)) != len(names):
+        raise SystemExit("--views %r names a view twice" % (value,))
+    if fmt == "raw":
+        raise SystemExit("--views does not go with --format raw: a raw video is one file with one image per frame; use png or npy")
+    return names
+
+
+def _check_views(ctx, names):
+    """before the first frame: the model offers every view asked for (CT_CLI_DEVICE=cpu: the torch restatements above, no more)"""
+    model = ctx.model
+    if ctx.scaled:
+        raise SystemExit("--views does not combine with the `inference` section (reduced-scale inference has no views())")
+    offered = CPU_VIEWS if ctx.on_cpu else tuple(getattr(model, "VIEWS", ())) if hasattr(model, "views") else ()
+    missing = [n for n in names if n not in offered]
+    if missing:
+        where = " under CT_CLI_DEVICE=cpu" if ctx.on_cpu else ""
+        raise SystemExit("--views: %s does not offer the view %s%s (it offers: %s)"
+                         % (type(model).__name__, ", ".join(map(repr, missing)), where, ", ".join(offered) or "none"))
+
+
 def _inference(cfg, model):
     """the optional `inference` section -> None, or the keyword arguments of model.forward_scaled"""
     sec = cfg.get("inference")
@@ -79,7 +134,7 @@ def _parse(argv):
                 cfg = yaml.safe_load(fh) or {}
         elif key == "--ckpt_path":
             ckpt = val
-        elif argv[0] == "predict" and key in ("--output", "--format"):
+        elif argv[0] == "predict" and key in ("--output", "--format", "--views"):
             opts[key[2:]] = val
         elif key.startswith("--"):
             _set(cfg, key[2:], val)
@@ -156,11 +211,14 @@ def main(argv=None, timing=None):
             raise SystemExit("predict needs `--output DIR`: the directory the corrected frames are written to")
         if opts.setdefault("format", "png") not in FORMATS:
             raise SystemExit("--format %r: one of %s" % (opts["format"], ", ".join(FORMATS)))
+        views = _view_names(opts["views"], opts["format"]) if "views" in opts else None
     ctx = _setup(cfg, ckpt)
     import torch.distributed as dist
     try:
         if argv[0] == "predict":
-            return _predict(ctx, opts["output"], opts["format"], cfg.get("writer") or {}, timing)
+            if views:
+                _check_views(ctx, views)
+            return _predict(ctx, opts["output"], opts["format"], cfg.get("writer") or {}, timing, views)
         return _test(ctx, timing)
     finally:
         if ctx.own_group:
@@ -241,7 +299,7 @@ def _test(ctx, timing):
     return tables[0]
 
 
-def _predict(ctx, output, fmt, writer_cfg, timing):
+def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
     import time
     import torch.distributed as dist
     from utils import sharding as sh
@@ -251,11 +309,13 @@ def _predict(ctx, output, fmt, writer_cfg, timing):
     depth, workers = int(writer_cfg.get("depth", 3)), int(writer_cfg.get("workers", 4))
     if not on_cpu:
         import ct_hip
+    takes_batch = bool(views) and not on_cpu and "batch" in inspect.signature(model.views).parameters
     written = 0
     for li, frames in enumerate(loaders):
         out_dir = os.path.join(output, "idx_%d" % li) if len(loaders) > 1 else output
         mine = sh.frames_of_rank(len(frames), rank, world)
-        grouped = (not ctx.scaled and not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "predict_group") and model.takes_groups())
+        grouped = (not views and not ctx.scaled and not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "predict_group")
+                   and model.takes_groups())
         if rank == 0:
             os.makedirs(out_dir, exist_ok=True)
             if fmt == "raw":
@@ -284,6 +344,16 @@ def _predict(ctx, output, fmt, writer_cfg, timing):
                     return
                 for n, (f, sample) in enumerate(prefetch(frames, indices, device)):
                     batch = {k: v.unsqueeze(0) for k, v in sample.items()}
+                    if views and not on_cpu:
+                        # ONE forward for the frame and all its views (freshly allocated uint8 frames: submit() holds them until
+                        # their download has run); the plain file is the `corrected` view, the bytes of the branches below
+                        want = views if "corrected" in views else ("corrected",) + views
+                        vs = (model.views(batch, names=want) if takes_batch else             # the Runner interface / the CNN modules
+                              model.views(batch["target"], batch["reference"], gt=batch.get("gt"), names=want))
+                        writer.submit([f], vs["corrected"])
+                        for name in views:
+                            writer.submit([f], vs[name], suffix=name)
+                        continue
                     if ctx.scaled:                              # reduced-scale inference: the full-size frame, clamped by the pack
                         corrected = model.forward_scaled(batch["target"], batch["reference"], **ctx.scaled)[0]
                     elif hasattr(model, "test_step"):           # the Runner interface: what test_step scores (methods/__init__.py:30)
@@ -292,6 +362,9 @@ def _predict(ctx, output, fmt, writer_cfg, timing):
                         corrected = model(batch["target"], batch["reference"], inference=True)[0]
                     if on_cpu:
                         writer.submit([f], quantise_u8(corrected).permute(0, 2, 3, 1).contiguous())
+                        for name in views or ():
+                            img = corrected if name == "corrected" else (chess_mix_cpu if name == "chess" else rgbmse_cpu)(batch["gt"], corrected)
+                            writer.submit([f], quantise_u8(img).permute(0, 2, 3, 1).contiguous(), suffix=name)
                         continue
                     corrected = corrected.float()
                     hwc = corrected.permute(0, 2, 3, 1)         # Runner.forward hands out a CHW view of HWC memory: no transpose then

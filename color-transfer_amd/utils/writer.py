@@ -13,6 +13,8 @@ reference until written: the caller must not modify them).
 Files are named by FRAME INDEX (`%06d.png`, `%06d.npy`; `raw`: frame f at offset f*H*W*3 of `frames.rgb`, rgb24, what
 `ffmpeg -f rawvideo -pix_fmt rgb24 -s WxH` reads), so the ranks of a sharded run write disjoint files -- or disjoint ranges of
 the one raw file -- into one directory and the result does not depend on the world size.  `null` downloads and drops.
+`submit(..., suffix="chess")` names its frames `%06d.chess.png` / `.npy` instead: further images of the same frame (the diagnostic
+views of `predict --views`) go through the same ring beside the frame itself; a raw video is one file and takes no suffix.
 
 The first error of a worker (unwritable directory, full disk) is kept and raised from the next `submit` or from `close()`."""
 import os
@@ -27,8 +29,8 @@ MAX_WORKERS = 16
 RAW_NAME = "frames.rgb"
 
 
-def frame_name(index, fmt):
-    return "%06d.%s" % (index, fmt)
+def frame_name(index, fmt, suffix=None):
+    return "%06d.%s" % (index, fmt) if suffix is None else "%06d.%s.%s" % (index, suffix, fmt)
 
 
 def truncate_raw(out_dir):
@@ -76,9 +78,10 @@ class FrameWriter:
             t.start()
 
     # ---- caller's side ---------------------------------------------------------------------------------------------------------
-    def submit(self, indices, frames_u8):
+    def submit(self, indices, frames_u8, suffix=None):
         """Queue frames_u8[j] for writing as frame indices[j].  Returns the event of the download (None for host tensors): a device
-        buffer handed in here may be overwritten by work that waits for it."""
+        buffer handed in here may be overwritten by work that waits for it.  suffix: None, or a name that goes between the frame
+        number and the extension (`%06d.<suffix>.png`); not with `raw`."""
         if self._closed:
             raise RuntimeError("FrameWriter is closed")
         self._raise_pending()
@@ -89,6 +92,11 @@ class FrameWriter:
             raise ValueError("%d frame indices for %d frames" % (len(indices), frames_u8.shape[0]))
         if any(i < 0 or (self.n_frames is not None and i >= self.n_frames) for i in indices):
             raise ValueError("frame index outside [0, %s)" % ("inf" if self.n_frames is None else self.n_frames))
+        if suffix is not None:
+            if not isinstance(suffix, str) or not suffix or any(ch in suffix for ch in "/\\.") or suffix != suffix.strip():
+                raise ValueError("suffix %r: a plain name without dots or path separators" % (suffix,))
+            if self.fmt == "raw":
+                raise ValueError("a raw video is one file: it takes no suffixed frames (suffix %r)" % (suffix,))
         if self.fmt == "raw":
             shape = tuple(frames_u8.shape[1:])
             if self._frame_shape is None:
@@ -123,7 +131,7 @@ class FrameWriter:
             slot.frames, slot.event = frames_u8, None
         slot.pending = k
         for j, index in enumerate(indices):
-            self._tasks.put((slot, j, index))
+            self._tasks.put((slot, j, index, suffix))
         return slot.event
 
     def close(self):
@@ -171,12 +179,12 @@ class FrameWriter:
             task = self._tasks.get()
             if task is None:
                 return
-            slot, j, index = task
+            slot, j, index, suffix = task
             try:
                 if not self._failed:                              # after an error the queue is only drained
                     if slot.event is not None:
                         slot.event.synchronize()
-                    self._write(index, slot.frames[j])
+                    self._write(index, slot.frames[j], suffix)
             except BaseException as e:                      # kept for the caller: never swallowed
                 with self._cond:
                     if not self._failed:
@@ -193,16 +201,16 @@ class FrameWriter:
             os.makedirs(self.out_dir, exist_ok=True)
             self._dir_made = True
 
-    def _write(self, index, frame):
+    def _write(self, index, frame, suffix=None):
         if self.fmt == "null":
             return
         self._ensure_dir()
         arr = frame.numpy()
         if self.fmt == "png":
             from PIL import Image
-            Image.fromarray(arr).save(os.path.join(self.out_dir, frame_name(index, "png")))
+            Image.fromarray(arr).save(os.path.join(self.out_dir, frame_name(index, "png", suffix)))
         elif self.fmt == "npy":
-            np.save(os.path.join(self.out_dir, frame_name(index, "npy")), arr)
+            np.save(os.path.join(self.out_dir, frame_name(index, "npy", suffix)), arr)
         else:
             with self._cond:
                 if self._raw_fd is None:

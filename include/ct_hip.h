@@ -576,6 +576,34 @@ int ct_scale_planes_f32(float *x, const float *gate, int planes, int plane, void
 int ct_upsample2_concat_f32(const float *x, const float *skip, float *out, int n, int cx, int cs, int h, int w,
                             void *stream);
 
+/* ---- diagnostic views: the image panel of the reference's log_images (methods/dcmcs3di.py:116-144, methods/dmsct.py:148-184),
+ * csrc/views.hip.  float32 NCHW in, as the models hold their tensors; entries added under ABI 9 (no argument list changed).
+ *
+ * ct_view_chess_mix_f32: utils/visualizations.py:9-21.  x, y, out [b][c][h][w]; block (i, j) of size x size pixels (ragged at the
+ *   bottom / right edge) comes from x when i + j is even, else from y.  Bitwise a copy.
+ * ct_view_scaled_plane_f32: the min-max family, out [b][3][h][w].
+ *   CT_VIEW_RGBMSE (visualizations.py:24-36, rgbmse): m = ((d0*d0 + d1*d1) + d2*d2) / 3 with d = x - y over the three channels of
+ *     x, y [b][3][h][w] (torch's channel mean, operation for operation); channel 0 = (m - lo) / (hi - lo) with lo / hi the
+ *     frame's own min / max of m, channels 1 and 2 = 0.
+ *   CT_VIEW_GRAY (no counterpart in the reference: how its logger shows a one-channel image): x [b][1][h][w], y unused (may be
+ *     NULL); all three channels = (x - lo) / (hi - lo).
+ *   hi == lo gives NaN (0 / 0, like the reference).  Finite inputs only: non-finite ones do not fault, their result is unspecified.
+ * ct_flow_to_image_u8: utils/flow_viz.py:184-264 (flow_to_image, what pred_flow_viz calls).  flow [b][2][h][w] -> out_hwc
+ *   [b][h][w][3] bytes.  Per frame: pixels with |u| or |v| > 1e7 are unknown -- zero flow for the maximum, black in the image; so
+ *   are NaN pixels (a deviation: the reference's own maximum turns NaN and with it the whole frame); maxrad = max sqrt(u^2 + v^2)
+ *   in float32; then, in float64 as numpy >= 2 promotes the reference's `u / (maxrad + eps)`: u, v /= maxrad + 2^-52, the angle
+ *   picks two neighbours of the 55-entry Middlebury wheel, radius <= 1 fades towards white, else x 0.75, floor(255 col).  An
+ *   all-zero flow is white.
+ * ws: 4-byte aligned, ct_view_workspace_bytes(b) bytes (the per-frame statistics; its content is private to one call).
+ * Three launches each for the last two (initialise, reduce, map); deterministic.                                          */
+#define CT_VIEW_RGBMSE 0
+#define CT_VIEW_GRAY 1
+int ct_view_chess_mix_f32(const float *x, const float *y, float *out, int b, int c, int h, int w, int size, void *stream);
+size_t ct_view_workspace_bytes(int b);
+int ct_view_scaled_plane_f32(const float *x, const float *y, float *out, void *ws, size_t ws_bytes, int b, int h, int w,
+                             int kind, void *stream);
+int ct_flow_to_image_u8(const float *flow, uint8_t *out_hwc, void *ws, size_t ws_bytes, int b, int h, int w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
