@@ -1,4 +1,4 @@
-// attention16.hip -- the streaming (online-softmax) attention of gmflow.hip with float32 operands as TWO fp16 pieces
+// attention16.hip -- the streaming (online-softmax) attention of attention_tokens.hip with float32 operands as TWO fp16 pieces
 // (11 + 11 mantissa bits) and three v_mfma_f32_32x32x16_f16 per 16-wide product (a_hi b_hi + a_hi b_lo + a_lo b_hi, float32
 // accumulation; what is dropped is 2^-22 relative) instead of three bf16 pieces and six MFMAs: half the matrix work, which is what
 // counts on real data (the 16-bit pipe runs into the chip's power limit: conv_ws.hip).  Replaces, same arguments and results to
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(256, 2) void attention16_colsum_kernel(const float 
     if (hl == 0 && kj < L) colsum[tb + kj] = acc;
 }
 
-// ---- launchers (called by the C entry points of gmflow.hip) ----------------------------------------------------------
+// ---- launchers (called by the C entry points of attention_tokens.hip) ----------------------------------------------------------
 bool attention16_enabled() {
     static const int on = [] { const char *e = getenv("CT_HIP_ATT16"); return e ? atoi(e) : 1; }();
     return on != 0;

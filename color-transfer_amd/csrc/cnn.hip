@@ -19,10 +19,9 @@
 // peak this path is priced against is the FP32 matrix rate, 157.3 TFLOP/s.
 #include "ct_common.h"
 #include "ct_conv.h"
+#include "ct_split.h"
 
 namespace ct {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kConvTH = 8;      // output rows per workgroup (two per wave)
 constexpr int kConvTW = 32;     // output columns per workgroup (= MFMA N)
@@ -37,21 +36,7 @@ constexpr int kNumCUs = 256;    // MI355X
 //          registers (43 VGPRs) while the current one is multiplied, so HBM/L2 latency hides under the MFMAs
 // ---------------------------------------------------------------------------------------------
 
-// GEN = false: the DCMCS3DI instantiations, which only know LeakyReLU(0.01) -- the full switch in the epilogue costs
-// them 1.5 % (measured r01)
-template <bool GEN>
-__device__ __forceinline__ float conv_act(float v, int act) {
-    if (!GEN) return v > 0.f ? v : 0.01f * v;
-    switch (act) {
-        case 1: return v > 0.f ? v : 0.01f * v;
-        case 2: return v > 0.f ? v : 0.f;
-        case 3: return 1.0f / (1.0f + expf(-v));
-        case 4: return tanhf(v);
-        case 5: return v / (1.0f + expf(-v));        // swish
-        default: return v;
-    }
-}
-
+// GEN = false: the DCMCS3DI instantiations, whose epilogue only knows LeakyReLU(0.01) (ct_split.h: act<GEN>)
 template <int KH, int KW, int MT, bool VEC, bool GEN>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, int tiles_x, int tiles_y, int n_tiles) {
     constexpr int PADY = KH / 2, PADX = KW / 2;
@@ -352,7 +337,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, int tiles
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             float v = acc[q][m][r];
-                            if (a.act) v = conv_act<GEN>(v, a.act);
+                            if (a.act) v = act<GEN>(v, a.act);
                             if (a.clamp) v = fminf(fmaxf(v, 0.f), 1.f);
                             stg[((r & 3) + 8 * (r >> 2) + 4 * hl) * 32 + nl] = v;
                         }
@@ -377,7 +362,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, int tiles
                             for (int r = 0; r < 16; ++r) {
                                 const int co = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
                                 float v = acc[q][m][r];
-                                if (a.act) v = conv_act<GEN>(v, a.act);
+                                if (a.act) v = act<GEN>(v, a.act);
                                 if (late_res && (full || co < cout_g)) v += res[(unsigned int)co * uplane + pix];
                                 if (a.clamp) v = fminf(fmaxf(v, 0.f), 1.f);
                                 if (full || co < cout_g) out[(unsigned int)co * uplane + pix] = v;
@@ -420,7 +405,7 @@ int launch_conv(const ConvArgs &a, int N, hipStream_t s) {
     return CT_OK;
 }
 
-// Stride-1 "same" convolutions with 64-channel output groups (GMFlow's backbone / refinement convs, gmflow.hip).
+// Stride-1 "same" convolutions with 64-channel output groups (GMFlow's backbone / refinement convs, conv_generic.hip).
 // Returns 1 when the geometry has no fast kernel (the caller then uses its generic one).
 int conv_fast(const ConvArgs &a, int N, int kh, int kw, hipStream_t s) {
     if (kh == 3 && kw == 3) return launch_conv<3, 3, 2, true>(a, N, s);

@@ -9,19 +9,10 @@
 // Weights arrive in ct_gconv2d_f32's packed layout: wp[coutp/64][kh*kw][ceil(cin/2)][2][64].
 #include "ct_common.h"
 #include "ct_conv.h"
+#include "ct_split.h"
 
 namespace ct {
 
-__device__ __forceinline__ float direct_act(float v, int act) {
-    switch (act) {
-        case 1: return v > 0.f ? v : 0.01f * v;
-        case 2: return v > 0.f ? v : 0.f;
-        case 3: return 1.0f / (1.0f + expf(-v));
-        case 4: return tanhf(v);
-        case 5: return v / (1.0f + expf(-v));
-        default: return v;
-    }
-}
 __device__ __forceinline__ float packed_w(const GConvArgs &a, int co, int ci, int tap) {
     const int cin_pairs = (a.cin + 1) / 2, taps = a.KH * a.KW;
     return a.wp[((((size_t)(co >> 6) * taps + tap) * cin_pairs + (ci >> 1)) * 2 + (ci & 1)) * 64 + (co & 63)];
@@ -93,7 +84,7 @@ __global__ __launch_bounds__(512) void conv_smallcout_kernel(GConvArgs a, int ti
         float *op = a.out + (size_t)n * a.out_bstride + (size_t)oy * a.Wo + ox;
         const size_t oplane = (size_t)a.Ho * a.Wo;
         const float v[4] = {s4.x, s4.y, s4.z, s4.w};
-        for (int co = 0; co < a.cout; ++co) op[co * oplane] = direct_act(v[co] + (a.bias ? a.bias[co] : 0.f), a.act);
+        for (int co = 0; co < a.cout; ++co) op[co * oplane] = act<true>(v[co] + (a.bias ? a.bias[co] : 0.f), a.act);
     }
 }
 
@@ -139,7 +130,7 @@ __global__ __launch_bounds__(256) void conv_smallcin_kernel(GConvArgs a, int co_
             acc = fmaf(x[4 * q], w4.x, acc); acc = fmaf(x[4 * q + 1], w4.y, acc);
             acc = fmaf(x[4 * q + 2], w4.z, acc); acc = fmaf(x[4 * q + 3], w4.w, acc);
         }
-        op[co * oplane] = direct_act(acc + (a.bias ? a.bias[co0 + co] : 0.f), a.act);
+        op[co * oplane] = act<true>(acc + (a.bias ? a.bias[co0 + co] : 0.f), a.act);
     }
 }
 

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
 #else
 #define CT_PHASE(i) do { } while (0)
 #endif
-    f32x16s acc[RPW][MT];
+    f32x16 acc[RPW][MT];
     // phase stagger of the two co-resident workgroups (see conv_mfma_kernel)
     if (n_stages >= 2 * n_chunks) {
         const unsigned int hw_wave_slot = __builtin_amdgcn_s_getreg(4 | (0 << 6) | ((4 - 1) << 11));   // HW_ID[3:0]
@@ -575,7 +575,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                     for (int qm = 0; qm < RPW * MT; ++qm) {            // rolled like the NCHW form below (code size)
                         const int q = qm >> 1, m = qm & 1;
                         const int y = ty * kSpTH + wave * RPW + q;
-                        f32x16s blk;
+                        f32x16 blk;
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
                             blk[r] = qm == 0 ? acc[0][0][r] : qm == 1 ? acc[0][1][r] : qm == 2 ? acc[1][0][r] : acc[1][1][r];
@@ -592,8 +592,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                                 float4 v = make_float4(__builtin_amdgcn_ldexpf(r0, un) + b4.x, __builtin_amdgcn_ldexpf(r1, un) + b4.y,
                                                        __builtin_amdgcn_ldexpf(r2, un) + b4.z, __builtin_amdgcn_ldexpf(r3, un) + b4.w);
                                 if (a.act) {
-                                    v.x = split_act<GEN>(v.x, a.act); v.y = split_act<GEN>(v.y, a.act);
-                                    v.z = split_act<GEN>(v.z, a.act); v.w = split_act<GEN>(v.w, a.act);
+                                    v.x = act<GEN>(v.x, a.act); v.y = act<GEN>(v.y, a.act);
+                                    v.z = act<GEN>(v.z, a.act); v.w = act<GEN>(v.w, a.act);
                                 }
                                 if (full || co < cout_g) *reinterpret_cast<float4 *>(op + co) = v;
                             }
@@ -609,7 +609,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                     for (int qm = 0; qm < RPW * MT; ++qm) {
                         const int q = qm >> 1, m = qm & 1;
                         const int y = ty * kSpTH + wave * RPW + q;
-                        f32x16s blk;
+                        f32x16 blk;
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
                             blk[r] = qm == 0 ? acc[0][0][r] : qm == 1 ? acc[0][1][r] : qm == 2 ? acc[1][0][r] : acc[1][1][r];
@@ -638,8 +638,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                                 if (res) rr = *reinterpret_cast<const float4 *>(res + o);
                                 if (a.res_pre) { v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
                                 if (a.act) {
-                                    v.x = split_act<GEN>(v.x, a.act); v.y = split_act<GEN>(v.y, a.act);
-                                    v.z = split_act<GEN>(v.z, a.act); v.w = split_act<GEN>(v.w, a.act);
+                                    v.x = act<GEN>(v.x, a.act); v.y = act<GEN>(v.y, a.act);
+                                    v.z = act<GEN>(v.z, a.act); v.w = act<GEN>(v.w, a.act);
                                 }
                                 if (!a.res_pre) { v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
                                 if (a.post_op) {
@@ -681,8 +681,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                                 const int co = m * 32 + 8 * j + 4 * hl;
                                 float4 v = make_float4(acc[q][m][4 * j], acc[q][m][4 * j + 1], acc[q][m][4 * j + 2], acc[q][m][4 * j + 3]);
                                 if (a.act) {
-                                    v.x = split_act<GEN>(v.x, a.act); v.y = split_act<GEN>(v.y, a.act);
-                                    v.z = split_act<GEN>(v.z, a.act); v.w = split_act<GEN>(v.w, a.act);
+                                    v.x = act<GEN>(v.x, a.act); v.y = act<GEN>(v.y, a.act);
+                                    v.z = act<GEN>(v.z, a.act); v.w = act<GEN>(v.w, a.act);
                                 }
                                 if (full || co < cout_g) *reinterpret_cast<float4 *>(op + co) = v;
                             }
@@ -698,7 +698,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         float v = acc[q][m][r];
-                        if (a.act) v = split_act<GEN>(v, a.act);
+                        if (a.act) v = act<GEN>(v, a.act);
                         if (a.clamp && !late_res) v = fminf(fmaxf(v, 0.f), 1.f);
                         stg[((r & 3) + 8 * (r >> 2) + 4 * hl) * 32 + nl] = v;
                     }

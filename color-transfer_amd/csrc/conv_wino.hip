@@ -341,7 +341,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                     y[i] += bv;
                     if constexpr (ACTK == 1) y[i] = fmaxf(y[i], 0.01f * y[i]);
                     else if constexpr (ACTK == 2) y[i] = fmaxf(y[i], 0.f);
-                    else if constexpr (ACTK == 3) y[i] = split_act<true>(y[i], a.act);
+                    else if constexpr (ACTK == 3) y[i] = act<true>(y[i], a.act);
                 }
                 if constexpr (HAS_RES) { y[0] += rq[j][0].x; y[1] += rq[j][0].y; y[2] += rq[j][1].x; y[3] += rq[j][1].y; }
                 if (a.clamp) {

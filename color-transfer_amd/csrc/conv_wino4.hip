@@ -289,7 +289,7 @@ __device__ __forceinline__ void do_op(St &st, const Ctx &cx, const LoadF &load_r
         float v = fmaf(st.y[k][a][c], unscale, cx.bias[k]);
         if constexpr (ACTK == 1) v = fmaxf(v, 0.01f * v);
         else if constexpr (ACTK == 2) v = fmaxf(v, 0.f);
-        else if constexpr (ACTK == 3) v = split_act<true>(v, cx.act);
+        else if constexpr (ACTK == 3) v = act<true>(v, cx.act);
         if constexpr (HAS_RES) v += st.rq[k][a][c];
         st.y[k][a][c] = v;
     } else if constexpr (o.kind == OP_MX) {     // pair landed in set TP ^ 1 ... of the step two ahead: the caller passes its set as TP

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
                 for (int i = 0; i < 4; ++i) rvv[i] = fmaxf(rvv[i], 0.f);
             } else if constexpr (ACTK == 3) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) rvv[i] = split_act<true>(rvv[i], a.act);
+                for (int i = 0; i < 4; ++i) rvv[i] = act<true>(rvv[i], a.act);
             }
             if (res != nullptr) { rvv[0] += rv.x; rvv[1] += rv.y; rvv[2] += rv.z; rvv[3] += rv.w; }   // uniform select
             if (a.clamp) {
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
             reduce_issue(r - 1);
             // two accumulators, alternating: a chain of MFMAs on ONE accumulator waits out the result latency of every link
             // while the partner wave is in its Y phase (measured: X = 2780 cycles for 1728 cycles of MFMA issue)
-            f32x16s acc, acc2;
+            f32x16 acc, acc2;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; }
             int e_cur = 0;

@@ -1,5 +1,5 @@
 // ct_attention16.h -- launchers of the two-piece fp16 streaming attention (attention16.hip), called by the C entry points of
-// gmflow.hip (ct_attention_tokens_f32, ct_attention_rows64_f32, ct_attention_colsum64_f32) unless CT_HIP_ATT16=0, and of
+// attention_tokens.hip (ct_attention_tokens_f32, ct_attention_rows64_f32, ct_attention_colsum64_f32) unless CT_HIP_ATT16=0, and of
 // disparity.hip (ct_attention_rows64_disp_f32)
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// ct_conv.h -- argument block of the LDS-tiled MFMA convolution (cnn.hip), shared with gmflow.hip
+// ct_conv.h -- argument block of the LDS-tiled MFMA convolution (cnn.hip), shared with conv_generic.hip
 #pragma once
 #include <hip/hip_runtime.h>
 

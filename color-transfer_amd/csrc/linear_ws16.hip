@@ -2,7 +2,7 @@
 // (three v_mfma_f32_32x32x16_f16 per 16-wide product, float32 accumulation; arithmetic and error model of conv_ws.hip /
 // attention16.hip).  Built for the FFN of a GMFlow transformer layer (unimatch/transformer.py:12-43,
 // mlp = Linear(256 -> 1024, no bias) . GELU . Linear(1024 -> 128, no bias)), whose two GEMMs were bound by operand delivery in the
-// LDS-tiled kernel of gmflow.hip (every 128 x 128 output tile re-staged its X tile and streamed its W slice):
+// LDS-tiled kernel of linear_tokens.hip (every 128 x 128 output tile re-staged its X tile and streamed its W slice):
 //   * a slice = 256 input channels x 128 output features of W = 128 KiB as fp16 (hi, lo) pieces: one persistent 8-wave workgroup
 //     per CU keeps ONE slice in LDS for its whole life and walks token tiles; no barrier after the prologue;
 //   * the activations never touch LDS: the B operand of D[feature][token] = W X^T wants, per lane, 8 consecutive channels of one
@@ -20,11 +20,11 @@
 #include <cstdint>
 #include <cmath>
 #include "ct_common.h"
+#include "ct_split.h"
 #include "../../include/ct_hip.h"
 
 namespace ct {
 
-typedef float f32x16w __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8w __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2w __attribute__((ext_vector_type(2)));
 
@@ -48,18 +48,6 @@ __device__ __forceinline__ int scale_exp_w(float mx, int none) {      // 2^e * m
     return min(max(ex, -100), 100);
 }
 __device__ __forceinline__ float pow2i_w(int e) { return __uint_as_float((unsigned int)(127 + e) << 23); }
-
-__device__ __forceinline__ float gelu_w(float v) {                    // gmflow.hip: gelu_as (A&S 7.1.26, branch free)
-    const float z = fabsf(v) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(z * z * -1.4426950408889634f);
-    const float erfc_half = 0.5f * p * t * e;
-    return v > 0.f ? v - v * erfc_half : v * erfc_half;
-}
 
 struct Ws16Args {
     const float *xa, *xb;          // token rows read by lane half 0 / 1 (slice 0): 128 channels each
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
     for (; tile < t_end; tile += 8) {
         const int next = tile + 8;
         const float4 *xn = row_ptr(next < t_end ? next : tile);
-        f32x16w acc[4];
+        f32x16 acc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -250,7 +238,7 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
                         v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
                     }
 #ifndef CT_W16_ABL_NOGELU
-                    if (a.act == 6) { v.x = gelu_w(v.x); v.y = gelu_w(v.y); v.z = gelu_w(v.z); v.w = gelu_w(v.w); }
+                    if (a.act == 6) { v.x = gelu_as(v.x); v.y = gelu_as(v.y); v.z = gelu_as(v.z); v.w = gelu_as(v.w); }
 #endif
                 }
                 stg[nl * 8 + ((2 * g + hl) ^ (nl & 7))] = v;

@@ -1,4 +1,4 @@
-"""Convolutions (csrc/cnn.hip, conv_split.hip, conv_ws.hip, conv_wino*.hip, conv1x1_rows.hip, gmflow.hip): the arithmetic
+"""Convolutions (csrc/cnn.hip, conv_split.hip, conv_ws.hip, conv_wino*.hip, conv1x1_rows.hip, conv_generic.hip): the arithmetic
 switches, ONE dispatch (_conv_entry) and the three front doors conv2d, conv2d_rows and gconv2d."""
 import os
 

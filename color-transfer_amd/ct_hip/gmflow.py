@@ -1,5 +1,5 @@
-"""GMFlow building blocks that are neither convolutions nor token layers (csrc/gmflow.hip): instance norm, elementwise
-steps, local correlation, warping, convex upsampling, the forward-backward check."""
+"""GMFlow building blocks that are neither convolutions nor token layers (csrc/gmflow.hip, local_corr.hip): instance norm,
+elementwise steps, local correlation, warping, convex upsampling, the forward-backward check."""
 import ctypes
 
 import torch

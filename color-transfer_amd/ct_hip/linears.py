@@ -1,4 +1,5 @@
-"""nn.Linear on channels-last tokens and LayerNorm(128): the exact, three-piece bf16 and weight-stationary fp16 kernels."""
+"""nn.Linear on channels-last tokens and LayerNorm(128) (csrc/linear_tokens.hip, linear_ws16.hip): the exact,
+three-piece bf16 and weight-stationary fp16 kernels."""
 import os
 
 import torch

@@ -6,7 +6,7 @@ num_reg_refine=6, pred_bidir_flow=True).
 Same parameter tree as the reference (`backbone.*`, `transformer.layers.N.*`, `feature_flow_attn.*`,
 `refine_proj.*`, `refine.*`) so pretrained checkpoints `load_state_dict` strictly; no
 network access: `pretrained` is None (random init) or a local checkpoint path.  All arithmetic runs in
-HIP kernels (csrc/gmflow.hip); torch only allocates, concatenates and permutes.  No CPU fallback.
+HIP kernels (csrc/conv_generic.hip, linear_tokens.hip, attention_tokens.hip, local_corr.hip, gmflow.hip); torch only allocates, concatenates and permutes.  No CPU fallback.
 The stereo / depth branches of UniMatch are dead code for this repository and are not implemented.
 """
 import math

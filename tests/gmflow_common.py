@@ -1,4 +1,5 @@
-"""Shared by tests/golden/make_golden_gmflow.py and the GMFlow tests: a procedural, seed-free state_dict.
+"""Shared by tests/golden/make_golden_gmflow.py and the GMFlow tests: a procedural, seed-free state_dict, test image pairs
+and the flow fields of the local-correlation tests.
 
 The GMFlow state (7.36 M parameters, 29 MB) is too big to commit, and in practice the matcher runs with
 pretrained weights, so the default init is irrelevant.  Every tensor is instead derived from its NAME:
@@ -44,3 +45,28 @@ def test_pair(seed, h, w, shift=5):
     img0 = (img0 + 0.15 * torch.rand(1, 3, h, w, generator=g)).clamp(0, 1)
     img1 = (torch.roll(img0, shifts=(2, shift), dims=(2, 3)) * 0.9 + 0.05).clamp(0, 1)
     return img0 * 255, img1 * 255
+
+
+def local_corr_flow_case(kind, b, h, w, rnd):
+    """The flow fields [b][2][h][w] that ct_local_corr_flow_f32 is tested on (h >= 21, w >= 41); rnd(*shape) draws normal noise."""
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    if kind == "smooth":
+        return torch.stack([0.07 * xx - 0.03 * yy + 0.4, 0.05 * yy + 0.02 * xx - 1.3], 0)[None].repeat(b, 1, 1, 1)
+    if kind == "constant":
+        flow = torch.full((b, 2, h, w), 2.25)
+        flow[:, 1] = -3.5
+    elif kind == "jump":
+        flow = torch.zeros(b, 2, h, w)
+        flow[:, 0, :, 17:] = 9.5                                  # a motion boundary through the tiles of column 16..23
+        flow[:, 1, 10:, :] = -6.25
+    elif kind == "random":
+        flow = rnd(b, 2, h, w) * 5
+    elif kind == "outside":
+        flow = torch.stack([0.9 * xx - 30.0, 0.0 * yy + 14.0], 0)[None].repeat(b, 1, 1, 1)     # windows leave the image on three sides
+        flow[1] = 300.0                                            # every window far outside: all zeros
+    else:
+        flow = rnd(b, 2, h, w)
+        flow[0, 0, 3, 5] = float("nan")
+        flow[1, 1, 20, 40] = float("inf")
+        flow[0, :, 8:12, 8:16] = float("nan")                     # a whole tile without a finite flow
+    return flow

@@ -1,5 +1,10 @@
-"""Unit parity of every GMFlow building-block kernel (csrc/gmflow.hip) against the torch op(s) of the reference it
-replaces, computed on the CPU in float64 where that is meaningful.  Tolerances are float32 rounding level."""
+"""Unit parity of every GMFlow building-block kernel (csrc/conv_generic.hip, linear_tokens.hip, attention_tokens.hip,
+local_corr.hip, gmflow.hip) against the torch op(s) of the reference it replaces, computed on the CPU
+in float64 where that is meaningful.  Tolerances are float32 rounding level."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -8,6 +13,7 @@ torch = pytest.importorskip("torch")
 import torch.nn.functional as F   # noqa: E402
 
 from oracle import gmflow as og   # noqa: E402
+from tests.gmflow_common import local_corr_flow_case   # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -508,32 +514,13 @@ def test_space_to_depth_and_shared_stride2_input(hip):
 
 @pytest.mark.parametrize("kind", ["smooth", "constant", "jump", "random", "outside", "nan"])
 def test_local_corr_flow_tile_form(hip, kind):
-    """ct_local_corr_flow_f32 in its tile form (csrc/gmflow.hip: a 4 x 8 pixel tile shares the box of its windows in LDS, one float32
+    """ct_local_corr_flow_f32 in its tile form (csrc/local_corr.hip: a 4 x 8 pixel tile shares the box of its windows in LDS, one float32
     MFMA GEMM per tile) against the reference's grid_sample formulation (oracle/gmflow.py, float64): smooth flows (the shared box),
     a flow discontinuity and random flows (boxes beyond the LDS budget: the per-pixel form inside the same launch), windows that
     leave the image partly or entirely, NaN / inf flows, ragged tiles at the right / bottom edges"""
     b, h, w = 2, 22, 43
     f0, f1 = rnd(b, 128, h, w), rnd(b, 128, h, w)
-    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
-    if kind == "smooth":
-        flow = torch.stack([0.07 * xx - 0.03 * yy + 0.4, 0.05 * yy + 0.02 * xx - 1.3], 0)[None].repeat(b, 1, 1, 1)
-    elif kind == "constant":
-        flow = torch.full((b, 2, h, w), 2.25)
-        flow[:, 1] = -3.5
-    elif kind == "jump":
-        flow = torch.zeros(b, 2, h, w)
-        flow[:, 0, :, 17:] = 9.5                                  # a motion boundary through the tiles of column 16..23
-        flow[:, 1, 10:, :] = -6.25
-    elif kind == "random":
-        flow = rnd(b, 2, h, w) * 5
-    elif kind == "outside":
-        flow = torch.stack([0.9 * xx - 30.0, 0.0 * yy + 14.0], 0)[None].repeat(b, 1, 1, 1)     # windows leave the image on three sides
-        flow[1] = 300.0                                            # every window far outside: all zeros
-    else:
-        flow = rnd(b, 2, h, w)
-        flow[0, 0, 3, 5] = float("nan")
-        flow[1, 1, 20, 40] = float("inf")
-        flow[0, :, 8:12, 8:16] = float("nan")                     # a whole tile without a finite flow
+    flow = local_corr_flow_case(kind, b, h, w, rnd)
     t0, t1 = f0.flatten(2).transpose(1, 2).contiguous(), f1.flatten(2).transpose(1, 2).contiguous()
     got = hip.local_corr_flow(t0.cuda(), t1.cuda(), flow.cuda(), 4).cpu().double()
     fin = torch.isfinite(flow).all(dim=1, keepdim=True)
@@ -553,6 +540,23 @@ def test_local_corr_softmax_tile_form(hip, b, h, w, r):
     t0, t1 = f0.flatten(2).transpose(1, 2).contiguous(), f1.flatten(2).transpose(1, 2).contiguous()
     close(hip.local_corr_softmax(t0.cuda(), t1.cuda(), h, w, r), og.local_correlation_softmax(f0.double(), f1.double(), r),
           "local_correlation_softmax, tile form", atol=2e-4, rtol=1e-4)
+
+
+def test_local_corr_per_pixel_kernels():
+    """local_corr_softmax_kernel and local_corr_flow_kernel, the stand-alone per-pixel forms that ct_local_corr_*_f32 launch with
+    CT_HIP_LCF_TILE=0 (or operands off 16-byte alignment), against the same float64 oracle and tolerances as the tile forms.  The
+    switch is read once per process, so the checks run in ONE child interpreter: test_local_corr_kernels (softmax 2x13x21 r=4, flow
+    2x13x21 with the rnd * 3 flow), the softmax of an image smaller than its window (1x3x5, r=2) and the 2x22x43 flows that leave
+    the image / are not finite."""
+    if os.environ.get("CT_HIP_LCF_TILE") == "0":
+        pytest.skip("this process already runs the per-pixel forms: it is the child of this test")
+    me = os.path.abspath(__file__)
+    ids = ["test_local_corr_kernels", "test_local_corr_softmax_tile_form[1-3-5-2]", "test_local_corr_flow_tile_form[outside]",
+           "test_local_corr_flow_tile_form[nan]"]
+    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider"] + [me + "::" + i for i in ids],
+                       cwd=os.path.dirname(os.path.dirname(me)), env=dict(os.environ, CT_HIP_LCF_TILE="0"), capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0 and "%d passed" % len(ids) in p.stdout, (p.stdout[-3000:], p.stderr[-1000:])
 
 
 def test_stride2_conv_in_a_graph_reads_fresh_data(hip):
