@@ -1,5 +1,5 @@
 """`python -m utils.cli test --config <yaml> [--model.func_spec ...] [--data.n_frames N] [--ckpt_path P]`
-`python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--views a,b,c] [--writer.depth D] [--writer.workers N] [...]`
+`python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--views a,b,c] [--writer.depth D] [--writer.workers N] [--writer.png_encoder host|device] [...]`
 both with `[--inference.scale_factor S] [--inference.antialias B]`
 
 A minimal look-alike of the reference's LightningCLI entry point (utils/cli.py:1-3, README.md:69-71) for the
@@ -22,6 +22,12 @@ before the first frame.  Not with `--format raw` (one file) and not with the `in
 `inference` (optional section, `inference: {scale_factor: 0.75, antialias: false}` or `--inference.scale_factor 0.75`): the model runs
 at a reduced size through its `forward_scaled` -- bicubic down, forward, bicubic back up, the reference's demo notebook, cell 24 -- and
 metrics / frames are those of the full-size result.  A model without `forward_scaled` is refused.  Without the section nothing changes.
+
+`predict --writer.png_encoder device` (with `--format png`, the default): the PNG files are compressed on the GPU -- row filters and
+a Huffman code per 16 rows (ct_hip.png_deflate, csrc/png.hip), one launch per group of frames or per view -- and the writer's threads
+only wrap the downloaded streams into the container (utils/png.py).  The files decode to the same pixels; they are larger than the
+host encoder's (no LZ77 matching).  It goes with `--views`; under CT_CLI_DEVICE=cpu it is refused before the first frame.  The default
+is `host`: PIL on the writer's threads, as before.
 """
 import importlib
 import inspect
@@ -212,6 +218,13 @@ def main(argv=None, timing=None):
         if opts.setdefault("format", "png") not in FORMATS:
             raise SystemExit("--format %r: one of %s" % (opts["format"], ", ".join(FORMATS)))
         views = _view_names(opts["views"], opts["format"]) if "views" in opts else None
+        from utils.writer import PNG_ENCODERS
+        encoder = (cfg.get("writer") or {}).get("png_encoder", "host")
+        if encoder not in PNG_ENCODERS:
+            raise SystemExit("--writer.png_encoder %r: one of %s" % (encoder, ", ".join(PNG_ENCODERS)))
+        if encoder == "device" and os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
+            raise SystemExit("--writer.png_encoder device needs a GPU: under CT_CLI_DEVICE=cpu the frames are host tensors and there "
+                             "is no device to encode on; use the default `host` encoder")
     ctx = _setup(cfg, ckpt)
     import torch.distributed as dist
     try:
@@ -371,7 +384,8 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
                     slot, u8 = pack(n, hwc, "hwc") if hwc.is_contiguous() else pack(n, corrected.contiguous(), "chw")
                     downloaded[slot] = writer.submit([f], u8)
 
-        writer = FrameWriter(out_dir, fmt, depth=depth, workers=workers, n_frames=len(frames), device=None if on_cpu else device)
+        writer = FrameWriter(out_dir, fmt, depth=depth, workers=workers, n_frames=len(frames), device=None if on_cpu else device,
+                             png_encoder=writer_cfg.get("png_encoder", "host"))
         with writer:
             if timing is not None and li == 0:
                 if grouped:

@@ -16,6 +16,14 @@ the one raw file -- into one directory and the result does not depend on the wor
 `submit(..., suffix="chess")` names its frames `%06d.chess.png` / `.npy` instead: further images of the same frame (the diagnostic
 views of `predict --views`) go through the same ring beside the frame itself; a raw video is one file and takes no suffix.
 
+`png_encoder="device"` (with `fmt="png"`): the compressed bytes of a PNG file are made on the GPU.  `submit` of a DEVICE tensor runs
+`ct_hip.png_deflate` on the caller's stream into a device buffer of the slot (filtered rows -> Huffman-coded deflate streams, one per
+16 rows), the slot's one asynchronous copy downloads the streams with their sizes and Adler-32 parts instead of the frames, and the
+workers only wrap them (`utils.png.assemble`: ~60 bytes of container and one CRC-32) and write the file.  The files decode to the
+same pixels as the host encoder's; they are larger (no LZ77 matching).  HOST tensors have no device to encode on: they keep the PIL
+path under `"device"` too.  Back-pressure, errors, suffixes and the returned event are those of the host encoder; the other formats
+ignore the option.
+
 The first error of a worker (unwritable directory, full disk) is kept and raised from the next `submit` or from `close()`."""
 import os
 import queue
@@ -25,6 +33,7 @@ import numpy as np
 import torch
 
 FORMATS = ("png", "npy", "raw", "null")
+PNG_ENCODERS = ("host", "device")
 MAX_WORKERS = 16
 RAW_NAME = "frames.rgb"
 
@@ -41,25 +50,61 @@ def truncate_raw(out_dir):
         pass
 
 
+class _EncodedFrame:
+    """frame j of a downloaded group of device-encoded frames"""
+    def __init__(self, group, j):
+        self.group, self.j = group, j
+
+    def file(self):
+        from utils import png
+        g, j = self.group, self.j
+        sizes, streams = g.sizes[j].tolist(), g.streams[j].numpy()
+        parts = [(s1, s2, rows * (1 + 3 * g.width)) for (s1, s2), rows in zip(g.adler[j].tolist(), png.chunk_rows(g.height, g.rows_per_chunk))]
+        return png.assemble(g.height, g.width, [streams[c, :size].tobytes() for c, size in enumerate(sizes)], parts)
+
+
+class _EncodedGroup:
+    """what the workers read of a device-encoded group: host views of the slot's pinned bytes (sizes, Adler-32 parts, streams)"""
+    def __init__(self, height, width, rows_per_chunk, sizes, adler, streams):
+        self.height, self.width, self.rows_per_chunk = height, width, rows_per_chunk
+        self.sizes, self.adler, self.streams = sizes, adler, streams
+
+    def __getitem__(self, j):
+        return _EncodedFrame(self, j)
+
+
+def _encoded_views(flat, k, chunks, cap):
+    """one flat uint8 buffer -> (sizes int32 [k, chunks], adler int32 [k, chunks, 2], streams uint8 [k, chunks, cap]) views of it"""
+    a, b = 4 * k * chunks, 12 * k * chunks
+    return (flat[:a].view(torch.int32).view(k, chunks), flat[a:b].view(torch.int32).view(k, chunks, 2),
+            flat[b:b + k * chunks * cap].view(k, chunks, cap))
+
+
 class _Slot:
     def __init__(self):
         self.buf = None             # pinned uint8 [capacity, H, W, 3] (device frames only)
+        self.dev = None             # device encoder: flat device bytes (sizes, Adler-32 parts, streams of a group)
+        self.enc = None             # device encoder: the pinned image of `dev`
         self.frames = None          # what the workers read: a view of buf, or the caller's host tensor
         self.event = None           # the download of `frames`
         self.pending = 0            # frames of this slot not yet written
 
 
 class FrameWriter:
-    def __init__(self, out_dir, fmt="png", depth=3, workers=4, n_frames=None, device=None):
+    def __init__(self, out_dir, fmt="png", depth=3, workers=4, n_frames=None, device=None, png_encoder="host"):
         """workers: an explicit small number (capped at 16), never derived from the machine's CPU count.  n_frames: the length of
-        the video, required for `raw` (the size of the file).  device: the GPU whose frames are submitted (default: the frames')."""
+        the video, required for `raw` (the size of the file).  device: the GPU whose frames are submitted (default: the frames').
+        png_encoder: "host" (PIL on the workers) or "device" (ct_hip.png_deflate; device tensors only, host tensors keep the PIL
+        path); only `png` looks at it."""
         if fmt not in FORMATS:
             raise ValueError("format %r: one of %s" % (fmt, ", ".join(FORMATS)))
+        if png_encoder not in PNG_ENCODERS:
+            raise ValueError("png_encoder %r: one of %s" % (png_encoder, ", ".join(PNG_ENCODERS)))
         if int(depth) < 1 or int(workers) < 1:
             raise ValueError("depth and workers must be >= 1 (got %r, %r)" % (depth, workers))
         if fmt == "raw" and n_frames is None:
             raise ValueError("format raw needs n_frames (frame f lives at offset f*H*W*3 of one file)")
-        self.out_dir, self.fmt = os.fspath(out_dir), fmt
+        self.out_dir, self.fmt, self.png_encoder = os.fspath(out_dir), fmt, png_encoder
         self.n_frames = None if n_frames is None else int(n_frames)
         self.device = None if device is None else torch.device(device)
         self._slots = [_Slot() for _ in range(int(depth))]
@@ -112,7 +157,9 @@ class FrameWriter:
                 self._cond.wait()
         self._raise_pending()
         k = len(indices)
-        if frames_u8.is_cuda:
+        if frames_u8.is_cuda and self.fmt == "png" and self.png_encoder == "device":
+            self._submit_encoded(slot, frames_u8)
+        elif frames_u8.is_cuda:
             dev = frames_u8.device
             if slot.buf is None or slot.buf.shape[1:] != frames_u8.shape[1:] or slot.buf.shape[0] < k:
                 slot.buf = torch.empty(tuple(frames_u8.shape), dtype=torch.uint8, pin_memory=True)
@@ -133,6 +180,31 @@ class FrameWriter:
         for j, index in enumerate(indices):
             self._tasks.put((slot, j, index, suffix))
         return slot.event
+
+    def _submit_encoded(self, slot, frames_u8):
+        """the device encoder: one png_deflate launch for the group on the caller's stream, then the slot's one copy"""
+        import ct_hip
+        dev = frames_u8.device
+        k, h, w, _ = frames_u8.shape
+        frames_u8 = frames_u8.contiguous()
+        chunks, cap = ct_hip.png_geometry(h, w, ct_hip.PNG_ROWS_PER_CHUNK)
+        need = k * chunks * (12 + cap)
+        if slot.dev is None or slot.dev.numel() < need or slot.dev.device != dev:
+            slot.dev = torch.empty(need, dtype=torch.uint8, device=dev)        # the old one is idle: the slot has nothing pending
+            slot.enc = torch.empty(need, dtype=torch.uint8, pin_memory=True)
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device if self.device is not None else dev)
+        sizes, adler, streams = _encoded_views(slot.dev, k, chunks, cap)
+        ct_hip.png_deflate(frames_u8, ct_hip.PNG_ROWS_PER_CHUNK, out=(streams, sizes, adler))
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(dev))
+        self._copy_stream.wait_event(ready)
+        with torch.cuda.stream(self._copy_stream):
+            slot.enc[:need].copy_(slot.dev[:need], non_blocking=True)
+            slot.event = torch.cuda.Event()
+            slot.event.record(self._copy_stream)
+        host_sizes, host_adler, host_streams = _encoded_views(slot.enc, k, chunks, cap)
+        slot.frames = _EncodedGroup(h, w, ct_hip.PNG_ROWS_PER_CHUNK, host_sizes, host_adler, host_streams)
 
     def close(self):
         """Drain the queue, join the workers, close the raw file, raise the first writer error.  Safe to call twice."""
@@ -205,6 +277,10 @@ class FrameWriter:
         if self.fmt == "null":
             return
         self._ensure_dir()
+        if isinstance(frame, _EncodedFrame):
+            with open(os.path.join(self.out_dir, frame_name(index, "png", suffix)), "wb") as fh:
+                fh.write(frame.file())
+            return
         arr = frame.numpy()
         if self.fmt == "png":
             from PIL import Image

@@ -604,6 +604,28 @@ int ct_view_scaled_plane_f32(const float *x, const float *y, float *out, void *w
                              int kind, void *stream);
 int ct_flow_to_image_u8(const float *flow, uint8_t *out_hwc, void *ws, size_t ws_bytes, int b, int h, int w, void *stream);
 
+/* ---- PNG serialisation: the compressed half of a PNG file, csrc/png.hip (the reference writes its frames as PNG files,
+ * utils/postprocess.py:138-144).  Entries added under ABI 9 (no argument list changed).
+ *
+ * ct_png_deflate_u8: frames [n][h][w][3] bytes (what ct_pack_u8_f32 and the views produce) -> per frame ceil(h / rows_per_chunk)
+ *   independent deflate streams (RFC 1951), one per chunk of rows_per_chunk rows (the last one may be short), each ending on a byte
+ *   boundary with non-final blocks only, so that a frame's chunks concatenate to one stream that an empty final block
+ *   (01 00 00 FF FF) closes.  Per row one PNG filter (0 .. 4) by the minimum sum of absolute values, the lowest type on a tie;
+ *   Up / Average / Paeth read the previous RAW row of the frame (zeros above row 0).  Per chunk either one dynamic-Huffman block of
+ *   literals only (code lengths <= 15 built on the device; one distance code of zero bits; header layout: csrc/png.hip) followed by
+ *   an empty stored block, or, when that would not be smaller, stored blocks of at most 65 535 bytes.
+ *   streams: slot (frame, chunk) at byte (frame * chunks + chunk) * capacity, any alignment; capacity >= ct_png_slot_capacity(h, w,
+ *     rows_per_chunk) = F + 5 ceil(F / 65535) + 5 with F = min(rows_per_chunk, h) * (3 w + 1) filtered bytes: no chunk is larger,
+ *     and bytes of a slot beyond its size are not written.
+ *   sizes [n][chunks] int32: the bytes of each stream.  adler [n][chunks][2] uint32: Adler-32 (s1, s2) of the chunk's filtered bytes
+ *     from the initial value 1; the host combines them (utils/png.py).
+ *   The bytes of a frame depend on that frame alone.  One launch, one workgroup per chunk, no workspace, asynchronous.
+ *   CT_E_BADARG: a null pointer, a size < 1, rows_per_chunk > 1024, w > 2^20 or a chunk of 2 GB (ct_png_slot_capacity returns 0
+ *   for those); CT_E_WORKSPACE: capacity too small or above 2^31 - 1; CT_E_ALIGN: sizes / adler not on 4 bytes.            */
+long long ct_png_slot_capacity(int h, int w, int rows_per_chunk);
+int ct_png_deflate_u8(const uint8_t *frames, int n, int h, int w, int rows_per_chunk, uint8_t *streams, long long capacity,
+                      int *sizes, unsigned int *adler, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

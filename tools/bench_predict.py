@@ -7,10 +7,15 @@
   * `utils.cli predict --format null` (the download ring without the disk) and `--format raw` (+ the box's disk / page cache)
     against `utils.cli test` on the same loader in the same process, alternated: `synthetic: video_u8`, --frames frames, group 8,
     `metrics: psnr`; the timing is main(..., timing=...)'s (one untimed warm pass inside it);
-  * `--format png` on --png-frames frames: host-bound (PIL encodes on the writer's workers), one number with the worker count.
+  * `--format png` on --png-frames frames with both encoders, same session, same frames, 16 workers: `host` (PIL encodes on the
+    writer's workers) and `device` (`--writer.png_encoder device`: ct_png_deflate_u8, csrc/png.hip, the workers only wrap the streams),
+    on the synthetic video (uniform random bytes) through `predict`; the sizes of the files of both encoders;
+  * ct_png_deflate_u8 alone, with events, on a group of 8 1080p frames of noise (stored chunks) and of a smooth ramp (Huffman
+    chunks): us per group, bytes in and out.
 
 usage: tools/bench_predict.py [--out profiles/predict_timing.json] [--frames 1000] [--reps 3] [--kernels-only] [--workdir DIR]
-For the copy / kernel overlap use rocprofv3 --kernel-trace --memory-copy-trace --stats -- python3 tools/bench_predict.py --trace-run."""
+For the copy / kernel overlap use rocprofv3 --kernel-trace --memory-copy-trace --stats -- python3 tools/bench_predict.py --trace-run
+(or --trace-png for the device PNG encoder)."""
 import argparse
 import contextlib
 import io
@@ -66,6 +71,31 @@ def kernels(reps, res):
     res["hbm_peak_tb_per_s"] = HBM_PEAK / 1e12
 
 
+def png_kernel(reps, res):
+    """ct_png_deflate_u8 alone on groups of 8: uniform noise (what the synthetic video holds: every chunk ends up stored) and
+    smooth frames (a ramp with +-3 grey levels of noise: every chunk Huffman-coded)"""
+    ramp = (torch.arange(W, device="cuda")[None, :, None] * 0.1 + torch.arange(H, device="cuda")[:, None, None] * 0.15 + torch.tensor([0.0, 40.0, 90.0], device="cuda"))
+    smooth = (ramp[None] + torch.randint(-3, 4, (8, H, W, 3), device="cuda")).clamp(0, 255).to(torch.uint8).contiguous()
+    groups = {"noise": torch.randint(0, 256, (8, H, W, 3), dtype=torch.uint8, device="cuda"), "smooth": smooth}
+    out = {}
+    for name, frames in groups.items():
+        bufs = ct_hip.png_deflate(frames)
+        torch.cuda.synchronize()
+        best = None
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(10):
+                ct_hip.png_deflate(frames, out=bufs)
+            b.record()
+            torch.cuda.synchronize()
+            ms = a.elapsed_time(b) / 10
+            best = ms if best is None else min(best, ms)
+        out[name] = {"us_per_group_of_8": 1e3 * best, "bytes_in": frames.numel(), "bytes_out": int(bufs[1].sum().item()),
+                     "chunks": int(bufs[1].numel()), "frames_per_s_kernel_alone": 8 / (best * 1e-3)}
+    res["png_deflate_1080p"] = out
+
+
 def _cli(cmd, frames, extra):
     from utils import cli
     timing = {}
@@ -86,7 +116,14 @@ def pipeline(frames, png_frames, reps, workdir, res):
         shutil.rmtree(os.path.join(workdir, "raw"), ignore_errors=True)
     workers = 16
     png = _cli("predict", png_frames, ["--output", os.path.join(workdir, "png"), "--format", "png", "--writer.workers", str(workers)])
-    shutil.rmtree(os.path.join(workdir, "png"), ignore_errors=True)
+    png_dev, sizes = [], {}
+    for _ in range(reps):
+        png_dev.append(_cli("predict", frames, ["--output", os.path.join(workdir, "png_dev"), "--format", "png", "--writer.workers", str(workers),
+                                                "--writer.png_encoder", "device"]))
+    for name in ("png", "png_dev"):                         # the first --png-frames files of both encoders: the same frames
+        d = os.path.join(workdir, name)
+        sizes[name] = sum(os.path.getsize(os.path.join(d, "%06d.png" % f)) for f in range(png_frames)) / png_frames
+        shutil.rmtree(d, ignore_errors=True)
     best = {k: max(v) for k, v in runs.items()}
     res["cli_video_u8_1080p"] = {
         "frames": frames, "group": 8, "frames_per_s_all": runs, "frames_per_s": best,
@@ -98,6 +135,10 @@ def pipeline(frames, png_frames, reps, workdir, res):
         "d2h_gb_per_s_predict_null": best["predict_null"] * H * W * 3 / 1e9,
         "raw_note": "predict_raw also measures this box's disk / page cache",
         "png": {"frames": png_frames, "frames_per_s": png, "workers": workers, "note": "host-bound: PIL encodes on the writer's workers"},
+        "png_device": {"frames": frames, "frames_per_s_all": png_dev, "frames_per_s": max(png_dev), "workers": workers,
+                       "over_png_host": max(png_dev) / png, "over_predict_null": max(png_dev) / best["predict_null"],
+                       "over_predict_raw": max(png_dev) / best["predict_raw"],
+                       "file_bytes_host": sizes["png"], "file_bytes_device": sizes["png_dev"], "file_size_ratio": sizes["png_dev"] / sizes["png"]},
     }
 
 
@@ -109,16 +150,22 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--trace-run", action="store_true", help="one short predict --format null pass and nothing else (for rocprofv3)")
+    ap.add_argument("--trace-png", action="store_true", help="one short predict --format png --writer.png_encoder device pass (for rocprofv3)")
     ap.add_argument("--workdir", default=None, help="where predict writes (default: a temporary directory, removed afterwards)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     workdir = a.workdir or tempfile.mkdtemp(prefix="bench_predict_")
     try:
+        if a.trace_png:
+            print("predict png (device encoder): %.1f frames/s" % _cli("predict", min(a.frames, 96), [
+                "--output", os.path.join(workdir, "png"), "--format", "png", "--writer.workers", "16", "--writer.png_encoder", "device"]))
+            return
         if a.trace_run:
             print("predict null: %.1f frames/s" % _cli("predict", min(a.frames, 96), ["--output", os.path.join(workdir, "null"), "--format", "null"]))
             return
         res = {"source_stamp": source_stamp(), "device": torch.cuda.get_device_name(0)}
         kernels(a.reps, res)
+        png_kernel(a.reps, res)
         if not a.kernels_only:
             pipeline(a.frames, a.png_frames, a.reps, workdir, res)
     finally:
