@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <cmath>
 #include "ct_attention16.h"
+#include "ct_env.h"
 
 namespace ct {
 
@@ -574,7 +575,7 @@ __global__ __launch_bounds__(256, 2) void attention16_colsum_kernel(const float 
 
 // ---- launchers (called by the C entry points of attention_tokens.hip) ----------------------------------------------------------
 bool attention16_enabled() {
-    static const int on = [] { const char *e = getenv("CT_HIP_ATT16"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("CT_HIP_ATT16", 1);
     return on != 0;
 }
 

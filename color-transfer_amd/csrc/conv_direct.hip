@@ -154,7 +154,7 @@ static int launch_smallcin(const GConvArgs &a, int N, hipStream_t s) {
 }
 
 int conv_direct(const GConvArgs &a, int N, hipStream_t s) {
-    static const int enabled = [] { const char *e = getenv("CT_HIP_CONV_DIRECT"); return e ? atoi(e) : 1; }();
+    static const int enabled = env_int("CT_HIP_CONV_DIRECT", 1);
     if (!enabled) return 1;
     if (a.cout <= 4 && a.KH == a.KW && (a.KH == 3 || a.KH == 1) && a.stride == 1 && a.padH == a.KH / 2 && a.padW == a.KW / 2) {
         const int tiles_x = (a.Wo + 31) / 32, tiles_y = (a.Ho + 1) / 2;

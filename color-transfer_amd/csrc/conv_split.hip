@@ -767,10 +767,10 @@ static int launch_split(const ConvArgs &a_in, int N, hipStream_t s) {
     const int tiles_x = (a.W + kSpTW - 1) / kSpTW, tiles_y = (a.H + kSpTH - 1) / kSpTH;
     const long long n_tiles = (long long)tiles_x * tiles_y * N * a.groups;
     if (n_tiles > 0x7fffffffLL) return CT_E_BADARG;
-    static const int wgs_per_cu = [] { const char *e = getenv("CT_HIP_SPLIT_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 2; }();
+    static const int wgs_per_cu = [] { int v = env_int("CT_HIP_SPLIT_WGS", 0); return v > 0 ? v : 2; }();
     const int grid = n_tiles < wgs_per_cu * kSpCUs ? (int)n_tiles : wgs_per_cu * kSpCUs;
     // stream-K only where whole units quantise badly: more units than resident workgroups and a last round that is mostly idle
-    static const bool sk_on = [] { const char *e = getenv("CT_HIP_SPLIT_SK"); return !(e && atoi(e) == 0); }();
+    static const bool sk_on = env_int("CT_HIP_SPLIT_SK", 1) != 0;
     const double rounds = (double)n_tiles / (double)grid;
     if (!(F16 && sk_on && a.sk_ws && a.rows_channels == 0 && wgs_per_cu == 2 && grid == 2 * kSpCUs && n_tiles > grid &&
           (double)((n_tiles + grid - 1) / grid) > 1.08 * rounds)) {

@@ -382,7 +382,7 @@ static unsigned long long *g_wn_prof = nullptr;
 
 // which Winograd kernel ct_conv3x3_wino16_f32 launches: 0 = conv_wino4.hip (four waves of 512 registers, pipelined; round 6, the
 // default), 1 = the eight-wave kernel of this file (round 5).  Process-wide, atomic; env CT_HIP_WINO_FORM presets it.
-static std::atomic<int> g_wino_form{[] { const char *e = getenv("CT_HIP_WINO_FORM"); return (e && e[0] == '1') ? 1 : 0; }()};
+static std::atomic<int> g_wino_form{[] { const char *e = env_str("CT_HIP_WINO_FORM"); return (e && e[0] == '1') ? 1 : 0; }()};
 
 // 1 = not this kernel's geometry
 int conv_wino(const ConvArgs &a, int N, hipStream_t s) {

@@ -486,7 +486,7 @@ static unsigned long long *g_ws_prof = nullptr;     // diagnostic build: every c
 
 // 1 = not this kernel's geometry (the caller falls back to conv_split_kernel)
 int conv_ws(const ConvArgs &a, int N, bool gen, hipStream_t s) {
-    static const int enabled = [] { const char *e = getenv("CT_HIP_CONV_WS"); return e ? atoi(e) : 1; }();
+    static const int enabled = env_int("CT_HIP_CONV_WS", 1);
 #ifndef CT_CONV_PROFILE
     if (a.prof != nullptr) return 1;
 #endif
@@ -507,7 +507,7 @@ int conv_ws(const ConvArgs &a, int N, bool gen, hipStream_t s) {
         const long long cost = rounds * ((sg + 2) / 3 * 3 + 2);      // steps run in threes; two halo rows of prologue
         if (best < 0 || cost < best) { best = cost; n_seg = ns_eff; seg = sg; }
     }
-    static const int forced_seg = [] { const char *e = getenv("CT_HIP_WS_SEG"); return e ? atoi(e) : 0; }();   // tuning only
+    static const int forced_seg = env_int("CT_HIP_WS_SEG", 0);   // tuning only
     if (forced_seg > 0) { seg = forced_seg < a.H ? forced_seg : a.H; n_seg = (a.H + seg - 1) / seg; }
     const long long n_items = cols * n_seg;
     if (n_items > 0x7fffffffLL) return CT_E_BADARG;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/ct_hip.h"
+#include "ct_env.h"      // ct::env_int / ct::env_str: the start-up switches
 
 namespace ct {
 
@@ -15,7 +16,7 @@ constexpr int kMaxBlocksPerImage = 1024;
 // total workgroups a streaming launch aims for: 256 CUs x 8 (guide: cap ~2048, grid-stride the rest)
 constexpr int kTargetBlocks = 2048;
 inline int target_blocks() {
-    static int v = [] { const char *e = getenv("CT_HIP_TARGET_BLOCKS"); int x = e ? atoi(e) : 0; return x > 0 ? x : kTargetBlocks; }();
+    static int v = [] { int x = env_int("CT_HIP_TARGET_BLOCKS", 0); return x > 0 ? x : kTargetBlocks; }();
     return v;
 }
 

@@ -16,6 +16,11 @@ bool eligible(int64_t n_pixels, bool any_size);
 // device workspace the launch needs for `batch` pairs (0 when not eligible)
 size_t ws_bytes(int64_t n_pixels, int batch);
 
+// true when the float32 output of `batch` pairs shares bytes with an input frame (target / reference / gt, elem_bytes per element;
+// gt may be null).  launch() refuses such a call with CT_E_BADARG; ct_reinhard_f32 / ct_reinhard_psnr_f32, whose two sweeps allow
+// out == target, ask first and keep the two sweeps then.
+bool overlaps(const float *out, const void *target, const void *reference, const void *gt, int64_t n_pixels, int batch, size_t elem_bytes);
+
 // Enqueue color_transfer_between_images (methods/linear.py:8-42) for `batch` pairs, optionally with the per-frame squared
 // error against gt (psnr_out: {mse, PSNR} per pair).  T = float (frames in [0,1]) or uint8_t (k / 255 as float32, the
 // reference's `.float() / 255`, utils/data.py:84,106,125).  Returns CT_OK or an error code; the caller checked eligible().

@@ -515,7 +515,7 @@ static int idt_grid(int64_t n, int batch) {
 }
 
 static int idt_minmax_grid(int64_t n, int batch) {
-    static const int per_call = [] { const char *e = getenv("CT_IDT_MINMAX_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+    static const int per_call = [] { const int v = env_int("CT_IDT_MINMAX_BLOCKS", 0); return v > 0 ? v : 256; }();
     int64_t want = (n / 4 + kIdtBlock - 1) / kIdtBlock;
     int64_t cap = per_call / (batch > 0 ? batch : 1);
     if (cap < 16) cap = 16;
@@ -523,7 +523,7 @@ static int idt_minmax_grid(int64_t n, int batch) {
     return want < 1 ? 1 : (int)want;
 }
 static int idt_apply_grid(int64_t n, int batch) {
-    static const int per_call = [] { const char *e = getenv("CT_IDT_APPLY_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : kTargetBlocks; }();
+    static const int per_call = [] { const int v = env_int("CT_IDT_APPLY_BLOCKS", 0); return v > 0 ? v : kTargetBlocks; }();
     int64_t want = (n + kIdtBlock - 1) / kIdtBlock;
     int64_t cap = per_call / (batch > 0 ? batch : 1);
     if (cap > 1024) cap = 1024;          // its 6 same-address atomicMax per workgroup again: 1024 beat 2048 by 4 % (one pair per call)
@@ -562,7 +562,7 @@ static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_
     // ~2 workgroups per CU (contended same-address atomics are an order of magnitude slower, MI355X_MICROARCH.md)
     int gh = idt_grid((n_t > n_r ? n_t : n_r) / 4 + 1, batch);
     {
-        static const int hist_cap = [] { const char *e = getenv("CT_IDT_HIST_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
+        static const int hist_cap = [] { const int v = env_int("CT_IDT_HIST_BLOCKS", 0); return v > 0 ? v : 512; }();
         int cap = 2 * hist_cap / batch;
         cap = cap > hist_cap ? hist_cap : (cap < 64 ? 64 : cap);
         if (gh > cap) gh = cap;                              // per pair

@@ -771,7 +771,7 @@ static thread_local hipEvent_t g_prof_evt[4] = {nullptr, nullptr, nullptr, nullp
 // float64 images always take the exact path.  Two levels: a process-wide default (ct_set_lab_mode / env CT_HIP_LAB; atomic) and a
 // per-thread override (ct_set_lab_mode_thread; -1 = none), so that two host threads driving different streams with different
 // modes do not race on one global -- every entry reads the mode once, through lab_mode(), on the calling thread.
-static std::atomic<int> g_lab_mode_default{[] { const char *e = getenv("CT_HIP_LAB"); return (e && e[0] == 'e') ? 1 : 0; }()};
+static std::atomic<int> g_lab_mode_default{[] { const char *e = env_str("CT_HIP_LAB"); return (e && e[0] == 'e') ? 1 : 0; }()};
 static thread_local int t_lab_mode = -1;
 static inline int lab_mode() { return t_lab_mode >= 0 ? t_lab_mode : g_lab_mode_default.load(std::memory_order_relaxed); }
 
@@ -787,7 +787,7 @@ static int resident_blocks(K kernel) {
     return per_cu * cus;
 }
 static int lut_blocks_per_image(int resident, int64_t n_tiles, int n_images) {
-    static int forced = [] { const char *e = getenv("CT_HIP_LUT_BLOCKS"); return e ? atoi(e) : 0; }();
+    static int forced = env_int("CT_HIP_LUT_BLOCKS", 0);
     const int total = forced > 0 ? forced : resident;
     int64_t want = (n_tiles + kLutWaves - 1) / kLutWaves;
     int64_t cap = total / (n_images > 0 ? n_images : 1);
@@ -883,6 +883,19 @@ static int rgb_meancov_impl(const T *rgb, int64_t n_pixels, int n_images, double
                                     (hipStream_t)stream);
 }
 
+// The two sweeps as the separate entries run them: ct_lab_stats_f32 on the targets, then on the references (each finished by
+// moments_finalize_kernel), then ct_reinhard_apply_f32 -- bit for bit the result of those three calls.  For the one case in which
+// the fused float32 entries may not take the persistent launch that is otherwise theirs (CT_HIP_REINHARD_PERSIST=1): an output
+// that overlaps an input, which include/ct_hip.h allows them (out == target) and rp::launch refuses.  Table arithmetic only.
+static int reinhard_separate_sweeps(const float *target, const float *reference, const float *gt, float *out, int64_t n_pixels, int batch,
+                                    double *stats, const WsLayout &l, double *sq, int *sq_blocks, hipStream_t s) {
+    int rc = launch_moments<float, true>(target, target, batch, batch, n_pixels, l, stats, s);
+    if (rc) return rc;
+    double *stats_r = stats + (size_t)batch * CT_LAB_STATS_STRIDE;
+    if ((rc = launch_moments<float, true>(reference, reference, batch, batch, n_pixels, l, stats_r, s))) return rc;    // same stream: the partial sums are free again
+    return launch_reinhard_apply<float, false>(target, stats, stats_r, out, n_pixels, batch, s, nullptr, 0, nullptr, gt, sq, sq_blocks);
+}
+
 template <typename T>
 static int reinhard_impl(const T *target, const T *reference, T *out, int64_t n_pixels, int batch,
                          double *stats_out, void *ws, size_t ws_bytes, void *stream) {
@@ -895,6 +908,11 @@ static int reinhard_impl(const T *target, const T *reference, T *out, int64_t n_
     if constexpr (sizeof(T) == 4) {
         // frames whose 1 / CUs share fits one CU's LDS: one persistent launch (reinhard_persist.hip) instead of the two sweeps
         if (lab_mode() == 0 && n_pixels > 0 && rp::eligible(n_pixels, false) && ws_bytes >= rp::ws_bytes(n_pixels, batch)) {
+            if (rp::overlaps(out, target, reference, nullptr, n_pixels, batch, sizeof(float))) {      // e.g. out == target
+                const WsLayout l = ws_carve(ws, 2 * batch);
+                return reinhard_separate_sweeps(target, reference, nullptr, out, n_pixels, batch, stats_out ? stats_out : l.stats, l, nullptr,
+                                                nullptr, (hipStream_t)stream);
+            }
             if (g_prof_evt[0]) (void)hipEventRecord(g_prof_evt[0], (hipStream_t)stream);
             if (g_prof_evt[1]) (void)hipEventRecord(g_prof_evt[1], (hipStream_t)stream);
             return rp::launch<float>(target, reference, nullptr, out, nullptr, n_pixels, batch, stats_out, ws, ws_bytes, (hipStream_t)stream,
@@ -981,6 +999,16 @@ static int reinhard_psnr_impl(const float *target, const float *reference, const
     if (batch == 0 || n_pixels == 0) return CT_OK;
     hipStream_t s = (hipStream_t)stream;
     if (lab_mode() == 0 && rp::eligible(n_pixels, false) && ws_bytes >= rp::ws_bytes(n_pixels, batch)) {
+        if (rp::overlaps(out, target, reference, gt, n_pixels, batch, sizeof(float))) {      // e.g. out == target: see reinhard_impl
+            const WsLayout l = ws_carve(ws, 2 * batch);
+            double *sq = reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + ws_bytes_for(2 * batch));
+            int sq_blocks = 0;
+            rc = reinhard_separate_sweeps(target, reference, gt, out, n_pixels, batch, stats_out ? stats_out : l.stats, l, sq, &sq_blocks, s);
+            if (rc) return rc;
+            hipLaunchKernelGGL(psnr_finish_kernel, dim3(batch), dim3(kBlock), 0, s, (const double *)sq, sq_blocks, n_pixels * 3, psnr_out);
+            CT_CHECK_LAUNCH();
+            return CT_OK;
+        }
         if (g_prof_evt[0]) (void)hipEventRecord(g_prof_evt[0], s);
         if (g_prof_evt[1]) (void)hipEventRecord(g_prof_evt[1], s);
         return rp::launch<float>(target, reference, gt, out, psnr_out, n_pixels, batch, stats_out, ws, ws_bytes, s, g_prof_evt[2], g_prof_evt[3]);

@@ -423,7 +423,7 @@ extern "C" {
 int ct_local_corr_softmax_f32(const float *f0, const float *f1, float *flow, int batch, int h, int w, int radius, void *stream) {
     if (!f0 || !f1 || !flow || batch < 0 || h < 1 || w < 1 || radius < 0 || (2 * radius + 1) * (2 * radius + 1) > 128) return CT_E_BADARG;
     if (batch == 0) return CT_OK;
-    static const bool tile_form = [] { const char *e = getenv("CT_HIP_LCF_TILE"); return !(e && atoi(e) == 0); }();
+    static const bool tile_form = ct::env_int("CT_HIP_LCF_TILE", 1) != 0;
     if (tile_form && (2 * radius + ct::kLcTY) * (2 * radius + ct::kLcTX) <= ct::kLcMaxP && (reinterpret_cast<uintptr_t>(f0) & 15) == 0 &&
         (reinterpret_cast<uintptr_t>(f1) & 15) == 0) {
         const int tiles_x = (w + ct::kLcTX - 1) / ct::kLcTX, tiles_y = (h + ct::kLcTY - 1) / ct::kLcTY;
@@ -443,7 +443,7 @@ int ct_local_corr_flow_f32(const float *f0, const float *f1, const float *flow, 
                            void *stream) {
     if (!f0 || !f1 || !flow || !corr || batch < 0 || h < 2 || w < 2 || radius < 0 || radius > 4) return CT_E_BADARG;
     if (batch == 0) return CT_OK;
-    static const bool tile_form = [] { const char *e = getenv("CT_HIP_LCF_TILE"); return !(e && atoi(e) == 0); }();
+    static const bool tile_form = ct::env_int("CT_HIP_LCF_TILE", 1) != 0;
     if (tile_form && (reinterpret_cast<uintptr_t>(f0) & 15) == 0 && (reinterpret_cast<uintptr_t>(f1) & 15) == 0) {
         const int tiles_x = (w + ct::kLcTX - 1) / ct::kLcTX, tiles_y = (h + ct::kLcTY - 1) / ct::kLcTY;
         hipLaunchKernelGGL(ct::local_corr_flow_tile_kernel, dim3((unsigned)(tiles_x * tiles_y), batch), dim3(256), 0, (hipStream_t)stream, f0, f1,

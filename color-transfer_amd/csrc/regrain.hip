@@ -330,7 +330,7 @@ int ct_regrain_f64(const double *img_in, const double *img_col, double *out, int
         hipLaunchKernelGGL(rg_weights_kernel, rg_grid(px), dim3(kBlock), 0, s, in_l[l], wt_l[l], h, w, 30.0 * exp2(-(double)l));
         CT_CHECK_LAUNCH();
         const double *prev = start;
-        static const int kblock = [] { const char *e = getenv("CT_HIP_REGRAIN_K"); const int v = e ? atoi(e) : kRgKMax; return v < 1 ? 1 : (v > kRgKMax ? kRgKMax : v); }();
+        static const int kblock = [] { const int v = env_int("CT_HIP_REGRAIN_K", kRgKMax); return v < 1 ? 1 : (v > kRgKMax ? kRgKMax : v); }();
         // small levels: small tiles (a launch lasts as long as its slowest workgroup: k sweeps of region / 256 pixels per thread)
         const int th = px > 200000 ? 16 : 8, tw = px > 200000 ? 32 : 16;
         const int tiles_x = (w + tw - 1) / tw, tiles_y = (h + th - 1) / th;

@@ -743,8 +743,8 @@ static int grid_size() {
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         (void)hipGetLastError();
         n = cus > 0 ? cus : 256;
-        const char *e = getenv("CT_HIP_PERSIST_WGS");
-        if (e && atoi(e) > 0 && atoi(e) <= n) n = atoi(e);      // never more workgroups than CUs: each needs a CU's LDS to itself
+        const int forced = env_int("CT_HIP_PERSIST_WGS", 0);
+        if (forced > 0 && forced <= n) n = forced;      // never more workgroups than CUs: each needs a CU's LDS to itself
         if (n > kMaxGrid) n = -1;
         cache[dev].store(n, std::memory_order_relaxed);
     }
@@ -761,7 +761,7 @@ bool eligible(int64_t n_pixels, bool any_size) {
     // The fused float32 entries (ct_reinhard_f32 / ct_reinhard_psnr_f32) keep the two sweeps unless CT_HIP_REINHARD_PERSIST=1: on
     // float32 frames both forms are bound by vector instruction issue, and this one executes 22 % more of them (DESIGN.md 4.1:
     // 33 - 34 k pairs/s against 36.5 k at 1080p); the uint8 entry and ct_reinhard_persist_f32 always come here.
-    static const bool on = [] { const char *e = getenv("CT_HIP_REINHARD_PERSIST"); return e && e[0] == '1'; }();
+    static const bool on = [] { const char *e = env_str("CT_HIP_REINHARD_PERSIST"); return e && e[0] == '1'; }();
     if (n_pixels < kTilePixels) return false;
     const int slots = slots_for(n_pixels);
     if (slots > kMaxSlots) return false;
@@ -792,8 +792,18 @@ static hipStream_t g_chain_stream[kMaxDevices];
 // waves per workgroup of the float32 instantiation: 16 (4 per SIMD, 128 registers: 54 of them spilled) or 8 (2 per SIMD, 256
 // registers, nothing spilled); CT_HIP_PERSIST_WAVES presets it (tuning)
 static int f32_waves() {
-    static const int v = [] { const char *e = getenv("CT_HIP_PERSIST_WAVES"); const int x = e ? atoi(e) : 0; return x == 8 || x == 16 ? x : CT_RP_F32_WAVES; }();
+    static const int v = [] { const int x = env_int("CT_HIP_PERSIST_WAVES", 0); return x == 8 || x == 16 ? x : CT_RP_F32_WAVES; }();
     return v;
+}
+
+bool overlaps(const float *out, const void *target, const void *reference, const void *gt, int64_t n_pixels, int batch, size_t elem_bytes) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (size_t)batch * n_pixels * 3 * sizeof(float);
+    const size_t in_bytes = (size_t)batch * n_pixels * 3 * elem_bytes;
+    for (const void *q : {target, reference, gt}) {
+        const uintptr_t q0 = reinterpret_cast<uintptr_t>(q);
+        if (q != nullptr && q0 < o1 && o0 < q0 + in_bytes) return true;
+    }
+    return false;
 }
 
 template <typename T>
@@ -802,14 +812,8 @@ int launch(const T *target, const T *reference, const T *gt, float *out, double 
     if (!eligible(n_pixels, true)) return CT_E_BADARG;
     if (ws == nullptr || (reinterpret_cast<uintptr_t>(ws) & 15) || ws_size < ws_bytes(n_pixels, batch)) return CT_E_WORKSPACE;
     if (gt != nullptr && psnr_out == nullptr) return CT_E_BADARG;
-    {   // out must not overlap an input frame: the exact redo of a flagged tile re-reads the input after the fast result is stored
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (size_t)batch * n_pixels * 3 * sizeof(float);
-        const size_t in_bytes = (size_t)batch * n_pixels * 3 * sizeof(T);
-        for (const T *q : {target, reference, gt}) {
-            const uintptr_t q0 = reinterpret_cast<uintptr_t>(q);
-            if (q != nullptr && q0 < o1 && o0 < q0 + in_bytes) return CT_E_BADARG;
-        }
-    }
+    // out must not overlap an input frame: the exact redo of a flagged tile re-reads the input after the fast result is stored
+    if (overlaps(out, target, reference, gt, n_pixels, batch, sizeof(T))) return CT_E_BADARG;
     const int g = grid_size();
     const int slots = slots_for(n_pixels);
     const int pslots = slots < kMaxParked ? slots : kMaxParked;
