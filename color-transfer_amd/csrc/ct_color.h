@@ -146,4 +146,21 @@ __device__ __forceinline__ T clip01(double v) {
     return o;
 }
 
+// ---- kornia.color.rgb_to_lab in float32, operation for operation (oracle/metrics.py:63-73): what iCID (metrics.hip) and the Lab
+// error maps (errmaps.hip) convert with.  Not the scikit-image arithmetic above: other constants, float32, no fused products.
+__device__ __forceinline__ float lab_f32(float v) {       // kornia rgb_to_lab: where(v > 0.008856, max(v, 0.008856)^(1/3), 7.787 v + 4/29)
+    return v > 0.008856f ? cbrtf(v) : fmaf(7.787f, v, 4.0f / 29.0f);
+}
+__device__ __forceinline__ float srgb_lin_f32(float c) {  // kornia rgb_to_linear_rgb
+    return c > 0.04045f ? powf((c + 0.055f) / 1.055f, 2.4f) : c / 12.92f;
+}
+__device__ __forceinline__ void rgb_to_lab_f32(float r, float g, float b, float &L, float &A, float &B) {
+    r = srgb_lin_f32(r); g = srgb_lin_f32(g); b = srgb_lin_f32(b);
+    const float x = (0.412453f * r + 0.357580f * g + 0.180423f * b) / 0.95047f;
+    const float y = 0.212671f * r + 0.715160f * g + 0.072169f * b;
+    const float z = (0.019334f * r + 0.119193f * g + 0.950227f * b) / 1.08883f;
+    const float fx = lab_f32(x), fy = lab_f32(y), fz = lab_f32(z);
+    L = 116.0f * fy - 16.0f; A = 500.0f * (fx - fy); B = 200.0f * (fy - fz);
+}
+
 }  // namespace ct

@@ -58,6 +58,11 @@ struct DynLdsAttr {
         if (e__ != hipSuccess) return (int)e__;     \
     } while (0)
 
+__device__ __forceinline__ int reflect(int i, int n) {     // torch "reflect" padding (no edge repeat); n >= 6 here
+    i = i < 0 ? -i : i;
+    return i >= n ? 2 * (n - 1) - i : i;
+}
+
 // ---- zeroing workspace words on the launch stream ---------------------------------------------------------------------------
 // A kernel of this library instead of hipMemsetAsync: captured in a hipGraph (torch.cuda.graph), a memset node in front of a
 // kernel was seen not to have run when that kernel read the words on replay, once any other call of the entry had preceded

@@ -12,6 +12,7 @@
 // 11-tap Gaussian (rows into LDS, then columns) for all 5 / 11 moment maps at once, evaluates the per-pixel formula and
 // reduces it to one float64 partial sum; a finishing kernel adds the partials in a fixed order (deterministic).  float32
 // arithmetic like the reference's torch code, float64 sums.
+#include "ct_color.h"
 #include "ct_common.h"
 
 namespace ct {
@@ -103,21 +104,6 @@ __global__ __launch_bounds__(kBlock) void ssim_tile_kernel(const float *__restri
 // -------------------------------------------------------------------------------------------------------------------
 constexpr int kIcTW = 32, kIcTH = 16;
 
-__device__ __forceinline__ float lab_f32(float v) {       // kornia rgb_to_lab: where(v > 0.008856, max(v, 0.008856)^(1/3), 7.787 v + 4/29)
-    return v > 0.008856f ? cbrtf(v) : fmaf(7.787f, v, 4.0f / 29.0f);
-}
-__device__ __forceinline__ float srgb_lin_f32(float c) {  // kornia rgb_to_linear_rgb
-    return c > 0.04045f ? powf((c + 0.055f) / 1.055f, 2.4f) : c / 12.92f;
-}
-__device__ __forceinline__ void rgb_to_lab_f32(float r, float g, float b, float &L, float &A, float &B) {
-    r = srgb_lin_f32(r); g = srgb_lin_f32(g); b = srgb_lin_f32(b);
-    const float x = (0.412453f * r + 0.357580f * g + 0.180423f * b) / 0.95047f;
-    const float y = 0.212671f * r + 0.715160f * g + 0.072169f * b;
-    const float z = (0.019334f * r + 0.119193f * g + 0.950227f * b) / 1.08883f;
-    const float fx = lab_f32(x), fy = lab_f32(y), fz = lab_f32(z);
-    L = 116.0f * fy - 16.0f; A = 500.0f * (fx - fy); B = 200.0f * (fy - fz);
-}
-
 // F.interpolate(scale_factor = 1/f, mode = "bilinear", align_corners = False) of one NCHW plane at output pixel (y, x)
 __device__ __forceinline__ float bilinear_down(const float *__restrict__ p, int H, int W, int f, int y, int x) {
     if (f == 1) return p[(size_t)y * W + x];
@@ -127,11 +113,6 @@ __device__ __forceinline__ float bilinear_down(const float *__restrict__ p, int 
     const float wy = sy - (float)y0, wx = sx - (float)x0;
     const float v00 = p[(size_t)y0 * W + x0], v01 = p[(size_t)y0 * W + x1], v10 = p[(size_t)y1 * W + x0], v11 = p[(size_t)y1 * W + x1];
     return (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
-}
-
-__device__ __forceinline__ int reflect(int i, int n) {     // torch "reflect" padding (no edge repeat); n >= 6 here
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * (n - 1) - i : i;
 }
 
 __global__ __launch_bounds__(kBlock) void icid_tile_kernel(const float *__restrict__ a, const float *__restrict__ b, int H, int W, int f, int h,

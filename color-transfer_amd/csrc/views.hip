@@ -7,10 +7,11 @@
 // nothing is reused, LDS holds only the four wave results of a reduction (and the 55-entry colour wheel).  The min-max family and
 // the flow image need a per-frame statistic first (min / max of the plane, the largest flow radius): a reduction pass leaves it in
 // the caller's workspace -- wave reduce, four waves through LDS, then ONE atomic min / max per workgroup on an order-preserving
-// integer image of the float (min and max do not depend on the order of their operands: the result is deterministic) -- and a map
+// integer image of the float (ct_minmax.h, shared with errmaps.hip) (min and max do not depend on the order of their operands: the result is deterministic) -- and a map
 // pass reads it back.  The Makefile's -ffp-contract=off keeps every product and sum below a rounding of its own: the map passes
 // recompute exactly the values the reductions saw.
 #include "ct_common.h"
+#include "ct_minmax.h"
 
 namespace ct {
 
@@ -47,32 +48,6 @@ __global__ __launch_bounds__(kBlock) void chess_mix_kernel(const float *__restri
     }
 }
 
-// ---- order-preserving integer image of a float32 --------------------------------------------------------------------------------
-// a < b as floats  <=>  key(a) < key(b) as unsigned (negative numbers: all bits flipped, others: sign bit set); -0 sorts below +0
-__device__ __forceinline__ unsigned int float_key(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(unsigned int k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// min / max of the workgroup's lanes; the result is valid in thread 0.  fminf / fmaxf drop a NaN operand.
-__device__ __forceinline__ void block_min_max(float &lo, float &hi, float *lds /* [2][4] */) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off, kWave));
-        hi = fmaxf(hi, __shfl_down(hi, off, kWave));
-    }
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
-    if (lane == 0) { lds[wid] = lo; lds[4 + wid] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        lo = fminf(fminf(lds[0], lds[1]), fminf(lds[2], lds[3]));
-        hi = fmaxf(fmaxf(lds[4], lds[5]), fmaxf(lds[6], lds[7]));
-    }
-}
-
 // ---- the min-max family ---------------------------------------------------------------------------------------------------------
 // torch.square(x - y).mean(dim=1) on a contiguous [B,3,H,W] tensor adds the channels in their order and divides by 3
 __device__ __forceinline__ float mse3(float x0, float x1, float x2, float y0, float y1, float y2) {
@@ -105,12 +80,6 @@ __device__ __forceinline__ float plane_value(const float *__restrict__ x, const 
     if constexpr (KIND == CT_VIEW_GRAY) return x[(int64_t)b * plane + p];
     const float *xb = x + (int64_t)b * 3 * plane + p, *yb = y + (int64_t)b * 3 * plane + p;
     return mse3(xb[0], xb[plane], xb[2 * plane], yb[0], yb[plane], yb[2 * plane]);
-}
-
-// keys[2 b] = key(+inf), keys[2 b + 1] = key(-inf): the neutral elements of the two atomics
-__global__ void minmax_init_kernel(unsigned int *__restrict__ keys, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 2 * n) keys[i] = (i & 1) ? 0x007fffffu : 0xff800000u;
 }
 
 // blockIdx.y strides over the frames, blockIdx.x over the plane.  vec: whole runs of four elements through 16-byte loads, the

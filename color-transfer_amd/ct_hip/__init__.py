@@ -35,7 +35,8 @@ from .attention import (attention_tokens, nchw_to_rows, nchw_to_tokens, pam_atte
                         pam_valid_rows, tokens_to_nchw)
 from .unet import dwconv, gconv2d_pad, scale_planes_, se_gate, upsample2_concat
 from .disparity import attention_rows64_index, pam_disp_fill, regress_disp
-from .views import CT_VIEW_GRAY, CT_VIEW_RGBMSE, chess_mix, flow_to_image, gray_view, rgbmse_view
+from .views import (CT_VIEW_ABMSE, CT_VIEW_GRAY, CT_VIEW_LABMSE, CT_VIEW_RGBMSE, abmse_view, chess_mix, flow_to_image, gray_view, labmse_view,
+                    rgbmse_view, rgbssim_view)
 from .png import PNG_ROWS_PER_CHUNK, png_deflate, png_geometry
 from . import _core
 

@@ -1,5 +1,5 @@
-"""Diagnostic views: the checkerboard mix, the min-max scaled error / disparity planes and the Middlebury flow colouring of the
-reference's image panel (utils/visualizations.py, utils/flow_viz.py; csrc/views.hip)."""
+"""Diagnostic views: the checkerboard mix, the min-max scaled error / disparity planes, the SSIM and Lab error maps and the Middlebury
+flow colouring of the reference's image panel (utils/visualizations.py, utils/flow_viz.py; csrc/views.hip, csrc/errmaps.hip)."""
 import torch
 
 from ._core import CtHipError, SIGNATURES, _c_int, _c_p, _c_sz, _f32c, _ptr, _stream, check, lib
@@ -9,9 +9,11 @@ SIGNATURES.update({
     "ct_view_workspace_bytes": (_c_sz, [_c_int]),
     "ct_view_scaled_plane_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "ct_flow_to_image_u8": (_c_int, [_c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_p]),
+    "ct_view_ssim_map_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_p]),
+    "ct_view_lab_map_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_p]),
 })
 
-CT_VIEW_RGBMSE, CT_VIEW_GRAY = 0, 1
+CT_VIEW_RGBMSE, CT_VIEW_GRAY, CT_VIEW_LABMSE, CT_VIEW_ABMSE = 0, 1, 2, 3
 
 
 def _nchw(x, name, channels=None):
@@ -43,19 +45,61 @@ def chess_mix(x, y, size=25):
     return out
 
 
+def _pair(x, y, name):
+    """the checks the error maps share: two float32 [B,3,H,W] device tensors of one shape on one device"""
+    _nchw(x, name, 3)
+    _nchw(y, name, 3)
+    if x.shape != y.shape or x.device != y.device:
+        raise CtHipError("%s: x of shape %s on %s, y of shape %s on %s" % (name, tuple(x.shape), x.device, tuple(y.shape), y.device))
+
+
 def rgbmse_view(x, y):
     """utils/visualizations.py:31-36 (rgbmse) on float32 [B,3,H,W] device tensors: channel 0 = the per-pixel mean over the channels
     of (x - y)^2, min-max scaled with the frame's own extremes; channels 1, 2 = 0.  A frame without any error is NaN (0 / 0, as in
     the reference; pack_u8 shows it black).  Deterministic; asynchronous on the current stream (ct_view_scaled_plane_f32)."""
-    _nchw(x, "rgbmse_view", 3)
-    _nchw(y, "rgbmse_view", 3)
-    if x.shape != y.shape or x.device != y.device:
-        raise CtHipError("rgbmse_view: x of shape %s on %s, y of shape %s on %s" % (tuple(x.shape), x.device, tuple(y.shape), y.device))
+    _pair(x, y, "rgbmse_view")
     b, _, h, w = x.shape
     out = torch.empty_like(x)
     ws, need = _stats(b, x.device)
     check(lib().ct_view_scaled_plane_f32(_ptr(x), _ptr(y), _ptr(out), _ptr(ws), need, b, h, w, CT_VIEW_RGBMSE, _stream()))
     return out
+
+
+def rgbssim_view(x, y):
+    """utils/visualizations.py:55-60 (rgbssim) on float32 [B,3,H,W] device tensors: channel 0 = 0.5 - ssim(x, y, window_size=11)
+    .mean(dim=1) / 2, min-max scaled with the frame's own extremes; channels 1, 2 = 0.  kornia.metrics.ssim is restated from its
+    published source (11-tap Gaussian of sigma 1.5, separable, reflect padding; parity unpinned).  Frames need more than 5 pixels
+    either way.  Deterministic; asynchronous on the current stream (ct_view_ssim_map_f32)."""
+    _pair(x, y, "rgbssim_view")
+    b, _, h, w = x.shape
+    if h < 6 or w < 6:
+        raise CtHipError("rgbssim_view: the reflect padding of 5 needs frames of more than 5 pixels either way (got %d x %d)" % (h, w))
+    out = torch.empty_like(x)
+    ws, need = _stats(b, x.device)
+    check(lib().ct_view_ssim_map_f32(_ptr(x), _ptr(y), _ptr(out), _ptr(ws), need, b, h, w, _stream()))
+    return out
+
+
+def _lab_view(x, y, name, kind):
+    _pair(x, y, name)
+    b, _, h, w = x.shape
+    out = torch.empty_like(x)
+    ws, need = _stats(b, x.device)
+    check(lib().ct_view_lab_map_f32(_ptr(x), _ptr(y), _ptr(out), _ptr(ws), need, b, h, w, kind, _stream()))
+    return out
+
+
+def labmse_view(x, y):
+    """utils/visualizations.py:39-44 (labmse) on float32 [B,3,H,W] device tensors: channel 0 = the mean of L, a, b of
+    rgb_to_lab((x - y)^2), min-max scaled with the frame's own extremes; channels 1, 2 = 0.  kornia.color.rgb_to_lab is restated
+    from its published source (parity unpinned).  Identical frames are NaN (a constant map: 0 / 0, as in the reference).
+    Deterministic; asynchronous on the current stream (ct_view_lab_map_f32)."""
+    return _lab_view(x, y, "labmse_view", CT_VIEW_LABMSE)
+
+
+def abmse_view(x, y):
+    """utils/visualizations.py:47-52 (abmse): labmse_view with the mean of a and b only."""
+    return _lab_view(x, y, "abmse_view", CT_VIEW_ABMSE)
 
 
 def gray_view(x):

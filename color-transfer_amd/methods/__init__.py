@@ -43,30 +43,35 @@ def fsim(x, y):
     return ct_hip.frame_fsim(x.float().contiguous(), y.float().contiguous())
 
 
-GT_VIEWS = ("chess", "rgbmse")          # the views that compare with the ground truth
+EXTRA_VIEWS = ("rgbssim", "labmse", "abmse")                      # every model with a ground truth has them, but only when named
+GT_VIEWS = ("chess", "rgbmse") + EXTRA_VIEWS                      # the views that compare with the ground truth
 
 
 def select_views(offered, names, have_gt):
     """The `names` argument of a model's views(): None = every offered view (without a ground truth: those that need none), a
-    comma-separated string or a sequence.  Unknown names, and a view that needs gt without one, raise ValueError."""
+    comma-separated string or a sequence.  The EXTRA_VIEWS are never part of the default: they come when named.  Unknown names,
+    and a view that needs gt without one, raise ValueError."""
     if names is None:
         return tuple(v for v in offered if have_gt or v not in GT_VIEWS)
     names = tuple(n.strip() for n in names.split(",")) if isinstance(names, str) else tuple(names)
-    bad = [n for n in names if n not in offered]
+    bad = [n for n in names if n not in offered and n not in EXTRA_VIEWS]
     if bad:
-        raise ValueError("unknown view%s %s: this model offers %s" % ("s" if len(bad) > 1 else "", ", ".join(map(repr, bad)), ", ".join(offered)))
+        raise ValueError("unknown view%s %s: this model offers %s, and by name only %s"
+                         % ("s" if len(bad) > 1 else "", ", ".join(map(repr, bad)), ", ".join(offered), ", ".join(EXTRA_VIEWS)))
     if not have_gt and any(n in GT_VIEWS for n in names):
         raise ValueError("the views %s compare with the ground truth: pass gt" % " and ".join(n for n in names if n in GT_VIEWS))
     return names
 
 
 def gt_views(view, corrected, gt):
-    """`corrected`, `chess` or `rgbmse` of float32 [B,3,H,W] device tensors as uint8 [B,H,W,3], the panel of the reference's
-    log_images (methods/dcmcs3di.py:131-135): pack_u8 of the frame, of chess_mix(gt, corrected), of rgbmse(gt, corrected)"""
+    """`corrected`, `chess`, `rgbmse`, `rgbssim`, `labmse` or `abmse` of float32 [B,3,H,W] device tensors as uint8 [B,H,W,3], the
+    panel of the reference's log_images (methods/dcmcs3di.py:131-135): pack_u8 of the frame, of chess_mix(gt, corrected), of
+    rgbmse(gt, corrected), of rgbssim(gt, corrected); labmse and abmse are the two maps of utils/visualizations.py it does not log"""
     import ct_hip
     if view == "corrected":
         return ct_hip.pack_u8(corrected, "chw")
-    fn = ct_hip.chess_mix if view == "chess" else ct_hip.rgbmse_view
+    fn = {"chess": ct_hip.chess_mix, "rgbmse": ct_hip.rgbmse_view, "rgbssim": ct_hip.rgbssim_view, "labmse": ct_hip.labmse_view,
+          "abmse": ct_hip.abmse_view}[view]
     return ct_hip.pack_u8(fn(gt, corrected), "chw")
 
 
@@ -146,7 +151,8 @@ class Runner(torch.nn.Module):
         """Diagnostic images of one batch as an ordered dict of uint8 [B,H,W,3] device tensors: `corrected` =
         pack_u8(forward(batch).clamp(0, 1)), and with batch["gt"] `chess` = pack_u8(chess_mix(gt, corrected)) and `rgbmse` =
         pack_u8(rgbmse_view(gt, corrected)).  One forward serves every view; each is bitwise what those public calls give one after
-        the other.  names: a subset (sequence or comma-separated string).  GPU only."""
+        the other.  names: a subset (sequence or comma-separated string); `rgbssim`, `labmse`, `abmse` = pack_u8(<name>_view(gt,
+        corrected)) come only when named (methods.EXTRA_VIEWS).  GPU only."""
         gt = batch.get("gt")
         names = select_views(self.VIEWS, names, gt is not None)
         corrected = self(batch).clamp(0, 1).float().contiguous()

@@ -184,6 +184,7 @@ class DCMCS3DI(torch.nn.Module):
             disparity     pack_u8(gray_view(disp_left)), forward_parts(want_disp=True)'s filled disparity, min-max scaled per frame
             warped_right  pack_u8(warped_rgb), the right view under the parallax attention
             occlusions    255 where valid_left is false
+            rgbssim, labmse, abmse    pack_u8(<name>_view(gt, corrected)): only when named (methods.EXTRA_VIEWS), need gt
         names: a subset (sequence or comma-separated string; default: all, without gt those that need none).  Unknown names and
         a gt view without gt raise ValueError.  ONE forward serves every view, and each is bitwise what the public pieces named
         above give when called one after the other."""

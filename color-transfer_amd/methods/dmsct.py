@@ -114,6 +114,7 @@ class DMSCT(torch.nn.Module):
             flow          flow_to_image(match["flow"]), the Middlebury colour code, each frame scaled by its own largest flow
             warped_right  pack_u8(flow_warp(reference, match["flow"]))
             occlusions    255 * match["fwd_occ"]
+            rgbssim, labmse, abmse    pack_u8(<name>_view(gt, corrected)): only when named (methods.EXTRA_VIEWS), need gt
         ONE match and one forward serve every view: the flow shown is the flow of `match`, computed at the reduced
         derive_matcher_inference_size -- the one the correction actually used.  (The reference's logging call runs the matcher a
         second time, at full size, for its panel.)  names, errors and the bitwise rule as for DCMCS3DI.views."""

@@ -14,7 +14,7 @@ with ONE collective (utils/sharding.py); rank 0 prints their means.
 img_as_ubyte(x.clip(0, 1)), utils/postprocess.py:138-144), downloaded through a ring of pinned buffers and written by frame index
 (utils/writer.py): every rank writes its own frames into the one directory, the result does not depend on the world size.
 
-`predict --views corrected,chess,rgbmse,...`: next to every corrected frame `%06d.<ext>` the listed diagnostic views of that frame, as
+`predict --views corrected,chess,rgbmse,rgbssim,...`: next to every corrected frame `%06d.<ext>` the listed diagnostic views of that frame, as
 `%06d.<view>.<ext>` -- the image panel of the reference's log_images, from the model's `views()` (methods/__init__.py, methods/dcmcs3di.py,
 methods/dmsct.py), one forward per frame for all of them.  Which views exist depends on the model; one it does not offer is refused
 before the first frame.  Not with `--format raw` (one file) and not with the `inference` section.  Without `--views` nothing changes.
@@ -63,8 +63,9 @@ def quantise_u8(x):
     return (x.clamp(0, 1).nan_to_num(0) * 255).round().to(torch.uint8)
 
 
-ALL_VIEWS = ("corrected", "chess", "rgbmse", "disparity", "flow", "warped_right", "occlusions")     # over all models
+ALL_VIEWS = ("corrected", "chess", "rgbmse", "disparity", "flow", "warped_right", "occlusions", "rgbssim", "labmse", "abmse")     # over all models
 CPU_VIEWS = ("corrected", "chess", "rgbmse")
+DEVICE_ONLY_VIEWS = ("rgbssim", "labmse", "abmse")     # methods.EXTRA_VIEWS: every model's views() takes them by name, no CPU stand-in
 
 
 def chess_mix_cpu(x, y, size=25):
@@ -104,7 +105,10 @@ def _check_views(ctx, names):
     model = ctx.model
     if ctx.scaled:
         raise SystemExit("--views does not combine with the `inference` section (reduced-scale inference has no views())")
-    offered = CPU_VIEWS if ctx.on_cpu else tuple(getattr(model, "VIEWS", ())) if hasattr(model, "views") else ()
+    if ctx.on_cpu and any(n in DEVICE_ONLY_VIEWS for n in names):
+        raise ValueError("--views: %s run on the device only (csrc/errmaps.hip): not under CT_CLI_DEVICE=cpu"
+                         % ", ".join(n for n in names if n in DEVICE_ONLY_VIEWS))
+    offered = CPU_VIEWS if ctx.on_cpu else tuple(getattr(model, "VIEWS", ())) + DEVICE_ONLY_VIEWS if hasattr(model, "views") else ()
     missing = [n for n in names if n not in offered]
     if missing:
         where = " under CT_CLI_DEVICE=cpu" if ctx.on_cpu else ""

@@ -1,8 +1,11 @@
-"""The reference's utils/visualizations.py on the device: `chess_mix`, `minmaxscale` and `rgbmse` with its signatures, on float32
-CUDA tensors (ct_hip.chess_mix / ct_hip.rgbmse_view / ct_hip.gray_view, csrc/views.hip).  No CPU path.
+"""The reference's utils/visualizations.py on the device: `chess_mix`, `minmaxscale`, `rgbmse`, `rgbssim`, `labmse` and `abmse` with
+its signatures, on float32 CUDA tensors (ct_hip.chess_mix / rgbmse_view / gray_view, csrc/views.hip; ct_hip.rgbssim_view /
+labmse_view / abmse_view, csrc/errmaps.hip).  No CPU path.
 
-`rgbssim`, `labmse` and `abmse` are not built: they rest on kornia's `ssim` / `rgb_to_lab`, third-party code that is not part of
-this stack and whose arithmetic could not be pinned; they raise NotImplementedError."""
+`rgbssim`, `labmse` and `abmse` rest on kornia's `ssim` / `rgb_to_lab`, third-party code that is not part of this stack: on the
+device its arithmetic is restated from the published source (parity unpinned for those two calls; the reference's own lines are
+pinned by tests/golden/errmaps.npz).  On the host the arithmetic would be kornia's itself: host tensors raise
+NotImplementedError."""
 import ct_hip
 
 
@@ -25,13 +28,17 @@ def rgbmse(x, y):
     return ct_hip.rgbmse_view(x.contiguous(), y.contiguous())
 
 
-def _needs_kornia(name, what):
+def _on_device(name, what, view):
     def fn(x, y):
-        raise NotImplementedError("%s needs kornia's %s, which this stack does not carry; rgbmse is the error map built here" % (name, what))
+        if not x.is_cuda:
+            raise NotImplementedError("%s on host tensors needs kornia's %s, which this stack does not carry; on CUDA tensors it runs "
+                                      "as ct_hip.%s" % (name, what, view.__name__))
+        return view(x.contiguous(), y.contiguous())
     fn.__name__ = name
+    fn.__doc__ = "visualizations.py (%s): [B,3,H,W] CUDA tensors -> ct_hip.%s" % (name, view.__name__)
     return fn
 
 
-labmse = _needs_kornia("labmse", "rgb_to_lab")
-abmse = _needs_kornia("abmse", "rgb_to_lab")
-rgbssim = _needs_kornia("rgbssim", "ssim")
+labmse = _on_device("labmse", "rgb_to_lab", ct_hip.labmse_view)
+abmse = _on_device("abmse", "rgb_to_lab", ct_hip.abmse_view)
+rgbssim = _on_device("rgbssim", "ssim", ct_hip.rgbssim_view)

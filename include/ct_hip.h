@@ -604,6 +604,27 @@ int ct_view_scaled_plane_f32(const float *x, const float *y, float *out, void *w
                              int kind, void *stream);
 int ct_flow_to_image_u8(const float *flow, uint8_t *out_hwc, void *ws, size_t ws_bytes, int b, int h, int w, void *stream);
 
+/* ---- the error maps of utils/visualizations.py that rest on kornia (rgbssim l.55-60, labmse l.39-44, abmse l.47-52),
+ * csrc/errmaps.hip.  Entries added under ABI 9 (no argument list changed).  x, y, out [b][3][h][w] float32; out as
+ * ct_view_scaled_plane_f32(CT_VIEW_RGBMSE) writes it: channel 0 = (m - lo) / (hi - lo) with the frame's own extremes of the
+ * map m, channels 1 and 2 = 0; hi == lo gives NaN.  kornia's arithmetic is restated from its published source (parity unpinned).
+ *
+ * ct_view_ssim_map_f32: m = 0.5 - mean_c(ssim_c) / 2, the channels added in their order and divided by 3.  Per channel, with
+ *   the normalised 11-tap Gaussian exp(-k^2 / (2 * 1.5^2)) applied along the rows, then the columns, under reflect padding of 5
+ *   (no edge repeat): mu1, mu2, E[x^2], E[y^2], E[xy]; s11 = E[x^2] - mu1^2, s22 = E[y^2] - mu2^2, s12 = E[xy] - mu1 mu2;
+ *   ssim = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2) + 1e-12), C1 = 0.01^2, C2 = 0.03^2.
+ *   h and w must exceed 5 (the reflect padding).
+ * ct_view_lab_map_f32: lab = kornia's rgb_to_lab of (x - y)^2 (sRGB 0.04045 / 2.4, XYZ, D65, 0.008856 / 7.787 / 4/29);
+ *   CT_VIEW_LABMSE: m = ((L + a) + b) / 3, CT_VIEW_ABMSE: m = (a + b) / 2.
+ * Both compute m once, into channel 0, and scale it in place.  ws as above.  CT_E_BADARG, before anything is launched, for a
+ * null pointer, b, h or w < 1, ws_bytes < ct_view_workspace_bytes(b), an unknown kind and, for the SSIM map, h < 6 or w < 6.
+ * Three launches each (initialise, map, scale); deterministic; float32 arithmetic throughout.                               */
+#define CT_VIEW_LABMSE 2
+#define CT_VIEW_ABMSE 3
+int ct_view_ssim_map_f32(const float *x, const float *y, float *out, void *ws, size_t ws_bytes, int b, int h, int w, void *stream);
+int ct_view_lab_map_f32(const float *x, const float *y, float *out, void *ws, size_t ws_bytes, int b, int h, int w, int kind,
+                        void *stream);
+
 /* ---- PNG serialisation: the compressed half of a PNG file, csrc/png.hip (the reference writes its frames as PNG files,
  * utils/postprocess.py:138-144).  Entries added under ABI 9 (no argument list changed).
  *

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the diagnostic-view kernels (csrc/views.hip) at 1080p with events, next to ct_pack_u8_f32 in the same session, and write a
+"""Time the diagnostic-view kernels (csrc/views.hip, csrc/errmaps.hip) at 1080p with events, next to ct_pack_u8_f32 in the same session, and write a
 stamped summary (tools/stamp.py).  Per entry: microseconds per call, the bytes the call has to move (inputs read once per pass,
 outputs written once), the achieved TB/s and the fraction of the 8 TB/s HBM peak:
 
@@ -8,6 +8,8 @@ outputs written once), the achieved TB/s and the fraction of the 8 TB/s HBM peak
     gray_view      two passes over one plane + three output planes                                   (8 + 12) B / pixel
     flow_to_image  two passes over u and v + three bytes                                             (16 + 3) B / pixel
     pack_u8 (chw)  4 read + 1 written per element: the yardstick                                          5 B / element
+    rgbssim_view / labmse_view / abmse_view (csrc/errmaps.hip), a group of 8 frames per call: the 6 planes of x and y read once,
+                   channel 0 written, then read and rewritten in place with channels 1 and 2  (24 + 16) B / pixel and frame
 
 The inputs rotate through a pool larger than the 256 MB last-level cache, so that a frame comes from HBM.  Nothing here is on a timed
 path and no time is gated; the numbers say where each kernel sits relative to the pack kernel on the same box.
@@ -64,6 +66,10 @@ def main():
     flows = [(x[:, :2] * 40 - 20).contiguous() for x in xs]
     disps = [(x[:, :1] * 200 - 100).contiguous() for x in xs]
     o8 = torch.empty((1, H, W, 3), dtype=torch.uint8, device="cuda")
+    group = 8                                                      # the error maps: a group of 8 frames per call
+    gpool = max(2, -(-pool // group))
+    gx = [torch.rand(group, 3, H, W, device="cuda") for _ in range(gpool)]
+    gy = [(g * 0.9 + 0.05 * torch.rand_like(g)).contiguous() for g in gx]
     cases = {
         "pack_u8_chw": (lambda i: ct_hip.pack_u8(xs[i], "chw", out=o8), 15 * plane),
         "chess_mix_25": (lambda i: ct_hip.chess_mix(xs[i], ys[i], 25), 24 * plane),
@@ -71,6 +77,9 @@ def main():
         "rgbmse_view": (lambda i: ct_hip.rgbmse_view(xs[i], ys[i]), 60 * plane),
         "gray_view": (lambda i: ct_hip.gray_view(disps[i]), 20 * plane),
         "flow_to_image": (lambda i: ct_hip.flow_to_image(flows[i]), 19 * plane),
+        "rgbssim_view_x8": (lambda i: ct_hip.rgbssim_view(gx[i % gpool], gy[i % gpool]), 40 * plane * group),
+        "labmse_view_x8": (lambda i: ct_hip.labmse_view(gx[i % gpool], gy[i % gpool]), 40 * plane * group),
+        "abmse_view_x8": (lambda i: ct_hip.abmse_view(gx[i % gpool], gy[i % gpool]), 40 * plane * group),
     }
     res = {"source_stamp": source_stamp(), "device": torch.cuda.get_device_name(0), "height": H, "width": W, "input_pool": pool,
            "hbm_peak_tb_per_s": HBM_PEAK / 1e12, "note": "times include the binding's allocation of the result (and, for the min-max "
@@ -79,7 +88,7 @@ def main():
         ms = timed(fn, pool, a.reps)
         res["kernels"][name] = {"us_per_call": 1e3 * ms, "bytes_per_call": nbytes, "tb_per_s": nbytes / (ms * 1e-3) / 1e12,
                                 "hbm_frac": nbytes / (ms * 1e-3) / HBM_PEAK}
-        print("%-14s %8.1f us  %6.2f TB/s  %5.1f %% of peak" % (name, 1e3 * ms, res["kernels"][name]["tb_per_s"], 100 * res["kernels"][name]["hbm_frac"]))
+        print("%-16s %8.1f us  %6.2f TB/s  %5.1f %% of peak" % (name, 1e3 * ms, res["kernels"][name]["tb_per_s"], 100 * res["kernels"][name]["hbm_frac"]))
     pack = res["kernels"]["pack_u8_chw"]["tb_per_s"]
     for k, v in res["kernels"].items():
         v["over_pack_tb_per_s"] = v["tb_per_s"] / pack
