@@ -64,4 +64,8 @@ int conv_ws(const ConvArgs &a, int N, bool gen, hipStream_t s);
 int conv_wino(const ConvArgs &a, int N, hipStream_t s);
 int conv_wino4(const ConvArgs &a, int N, hipStream_t s);
 
+// conv_split.hip: sticky status of the current device for ct_device_status (abi.hip): 1 = a stream-K consumer gave up waiting
+// for its producer since the last clear, -1 = the device could not be read
+int conv_split_read_status(bool clear);
+
 }  // namespace ct

@@ -1,0 +1,17 @@
+// ct_metrics.h -- host-side interface of metrics.hip for linear.hip: the two launches of the per-frame PSNR (a kernel can
+// only be launched from the source that defines it).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ct {
+
+// float64 partial sums of (a - b)^2 over `batch` frames of n elements: partials[frame][kMaxBlocksPerImage], *n_blocks of
+// them written per frame.  Returns CT_OK or a HIP error.
+int launch_sqerr_partials(const float *a, const float *b, int64_t n, int batch, double *partials, int *n_blocks, hipStream_t s);
+
+// out[frame] = {mse, PSNR} from n_blocks partial sums per frame (launch_sqerr_partials' or the apply sweep's), added in a
+// fixed order
+int launch_psnr_finish(const double *partials, int n_blocks, int64_t n, int batch, double *out, hipStream_t s);
+
+}  // namespace ct

@@ -1,6 +1,7 @@
-// ct_reinhard.h -- device helpers shared by the Reinhard kernels of linear.hip (two sweeps) and reinhard_persist.hip
-// (one persistent launch): Lab moment accumulation, the statistics record, the affine map in the cube-root domain and
-// the 256-pixel tile I/O of the table path.  Replaces the numpy expressions of methods/linear.py:25-40.
+// ct_reinhard.h -- device helpers shared by the Reinhard kernels of linear.hip (two sweeps), reinhard_persist.hip (one
+// persistent launch) and the generic moments sweep of ct_moments.h (which mk.hip runs on RGB): moment accumulation, the
+// statistics record, the affine map in the cube-root domain and the 256-pixel tile I/O of the table path.  Replaces the
+// numpy expressions of methods/linear.py:25-40.
 #pragma once
 #include "ct_color.h"
 #include "ct_color_lut.h"

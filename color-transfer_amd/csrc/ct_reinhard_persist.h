@@ -1,4 +1,5 @@
-// ct_reinhard_persist.h -- host-side interface of reinhard_persist.hip (the one-launch Reinhard transfer) for linear.hip.
+// ct_reinhard_persist.h -- host-side interface of reinhard_persist.hip (the one-launch Reinhard transfer) for linear.hip
+// (the dispatch of the fused entries) and abi.hip (ct_device_status).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

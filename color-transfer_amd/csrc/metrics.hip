@@ -7,13 +7,17 @@
 // sources (oracle/metrics.py says where) -- "parity unpinned" for those calls; SSIM's core is anchored on scikit-image's
 // structural_similarity, iCID's own lines on a run of the reference's utils/icid.py (tests/golden/make_golden_*).
 //
-// Both are ONE fused pass per frame: a workgroup owns a 32x32 (SSIM) / 32x16 (iCID) tile of the metric map, brings the
+//   PSNR  = a float64 squared-error sweep and its finish (at the end of this file; linear.hip's fused Reinhard + PSNR entry
+//           launches the same two kernels through ct_metrics.h)
+//
+// SSIM and iCID are ONE fused pass per frame: a workgroup owns a 32x32 (SSIM) / 32x16 (iCID) tile of the metric map, brings the
 // down-sampled inputs (plus a 5-pixel halo) into LDS straight from the full-resolution NCHW planes, runs the separable
 // 11-tap Gaussian (rows into LDS, then columns) for all 5 / 11 moment maps at once, evaluates the per-pixel formula and
 // reduces it to one float64 partial sum; a finishing kernel adds the partials in a fixed order (deterministic).  float32
 // arithmetic like the reference's torch code, float64 sums.
 #include "ct_color.h"
 #include "ct_common.h"
+#include "ct_metrics.h"
 
 namespace ct {
 
@@ -211,6 +215,58 @@ static int metric_factor(int height, int width) {          // max(1, round(min(H
     return r < 1.0 ? 1 : (int)r;
 }
 
+// -------------------------------------------------------------------------------------------
+// Per-frame PSNR (the metric Runner.test_step logs, methods/__init__.py:32,37; piq.psnr semantics: inputs
+// clamped by the caller, data_range 1, mean squared error over all elements of a frame, 10 log10(1/mse)).
+// Deterministic: float64 partial sums per workgroup, fixed-order finish.  grid = (G, batch).
+// -------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void sqerr_partial_kernel(const float *__restrict__ a, const float *__restrict__ b,
+                                                               int64_t n, double *__restrict__ partials) {
+    __shared__ double lds[4];
+    const float *pa = a + (size_t)blockIdx.y * n, *pb = b + (size_t)blockIdx.y * n;
+    double s[1] = {0.0};
+    const bool vec = ((reinterpret_cast<uintptr_t>(pa) | reinterpret_cast<uintptr_t>(pb)) & 15) == 0;
+    const int64_t n4 = vec ? (n >> 2) : 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
+        const float4 x = reinterpret_cast<const float4 *>(pa)[i], y = reinterpret_cast<const float4 *>(pb)[i];
+        const double d0 = (double)x.x - y.x, d1 = (double)x.y - y.y, d2 = (double)x.z - y.z, d3 = (double)x.w - y.w;
+        s[0] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double d = (double)pa[i] - pb[i];
+        s[0] += d * d;
+    }
+    block_sum<1>(s, lds);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.y * kMaxBlocksPerImage + blockIdx.x] = s[0];
+}
+
+__global__ __launch_bounds__(kBlock) void psnr_finish_kernel(const double *__restrict__ partials, int n_blocks, int64_t n,
+                                                             double *__restrict__ out) {
+    __shared__ double lds[4];
+    double s[1] = {0.0};
+    for (int i = threadIdx.x; i < n_blocks; i += kBlock) s[0] += partials[(size_t)blockIdx.x * kMaxBlocksPerImage + i];
+    block_sum<1>(s, lds);
+    if (threadIdx.x == 0) {
+        const double mse = s[0] / (double)n;
+        out[blockIdx.x * 2] = mse;
+        out[blockIdx.x * 2 + 1] = 10.0 * log10(1.0 / (mse > 1e-300 ? mse : 1e-300));
+    }
+}
+
+int launch_sqerr_partials(const float *a, const float *b, int64_t n, int batch, double *partials, int *n_blocks, hipStream_t s) {
+    const int G = blocks_per_image(n >> 2, batch);
+    *n_blocks = G;
+    hipLaunchKernelGGL(sqerr_partial_kernel, dim3(G, batch), dim3(kBlock), 0, s, a, b, n, partials);
+    CT_CHECK_LAUNCH();
+    return CT_OK;
+}
+
+int launch_psnr_finish(const double *partials, int n_blocks, int64_t n, int batch, double *out, hipStream_t s) {
+    hipLaunchKernelGGL(psnr_finish_kernel, dim3(batch), dim3(kBlock), 0, s, partials, n_blocks, n, out);
+    CT_CHECK_LAUNCH();
+    return CT_OK;
+}
+
 }  // namespace ct
 
 extern "C" {
@@ -254,6 +310,16 @@ int ct_frame_icid_f32(const float *a, const float *b, int height, int width, int
                        (int)(grid.x * grid.y), (double)h * w, -1.0, 1.0, out);
     CT_CHECK_LAUNCH();
     return CT_OK;
+}
+
+int ct_frame_psnr_f32(const float *a, const float *b, int64_t n_elems, int batch, double *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!a || !b || !out || n_elems < 1 || batch < 0) return CT_E_BADARG;
+    if (!ws || ws_bytes < (size_t)batch * ct::kMaxBlocksPerImage * sizeof(double)) return CT_E_WORKSPACE;
+    if (batch == 0) return CT_OK;
+    int G = 0;
+    const int rc = ct::launch_sqerr_partials(a, b, n_elems, batch, (double *)ws, &G, (hipStream_t)stream);
+    if (rc) return rc;
+    return ct::launch_psnr_finish((const double *)ws, G, n_elems, batch, out, (hipStream_t)stream);
 }
 
 }  // extern "C"
