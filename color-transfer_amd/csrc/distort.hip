@@ -10,20 +10,9 @@
 // (optional): that frame / 255 as float32 [3][H][W] -- the `target / 255` the dataset hands to the model
 // (utils/data.py:125).  One elementwise sweep; contrast needs the mean of the grey image first (exact integer sum).
 #include "ct_common.h"
+#include "ct_distort.h"
 
 namespace ct {
-
-enum { kDistIdentity = 0, kDistBrightness = 1, kDistContrast = 2, kDistSaturation = 3, kDistHue = 4, kDistGamma = 5 };
-
-__device__ __forceinline__ float gray_u8(float r, float g, float b) {           // rgb_to_grayscale(...).to(uint8): truncation
-    return truncf(0.2989f * r + 0.587f * g + 0.114f * b);
-}
-// _blend(...).clamp(0, 255).to(uint8); ratio and 1 - ratio are Python floats (float64) in torchvision, each rounded to
-// float32 when it meets the tensor -- 1 - ratio is therefore formed in float64 on the host (one_minus), not as 1.0f - ratio
-__device__ __forceinline__ float blend_u8(float a, float b, float ratio, float one_minus) {
-    return truncf(fminf(fmaxf(ratio * a + one_minus * b, 0.f), 255.f));
-}
-__device__ __forceinline__ float to_u8(float x) { return truncf(x * 255.999f); }  // convert_image_dtype(float -> uint8): mul(255 + 1 - 1e-3)
 
 __global__ __launch_bounds__(kBlock) void gray_sum_kernel(const uint8_t *__restrict__ in, int64_t n, unsigned long long *__restrict__ sum) {
     __shared__ unsigned long long red[4];
@@ -42,49 +31,8 @@ __global__ __launch_bounds__(kBlock) void distort_kernel(const uint8_t *__restri
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     float r = (float)in[i], g = (float)in[n + i], b = (float)in[2 * n + i];
-    if (kind == kDistBrightness) {
-        r = blend_u8(r, 0.f, param, one_minus); g = blend_u8(g, 0.f, param, one_minus); b = blend_u8(b, 0.f, param, one_minus);
-    } else if (kind == kDistContrast) {
-        const float mean = (float)((double)gray_sum[0] / (double)n);           // torch.mean of the uint8 grey image, in float32
-        r = blend_u8(r, mean, param, one_minus); g = blend_u8(g, mean, param, one_minus); b = blend_u8(b, mean, param, one_minus);
-    } else if (kind == kDistSaturation) {
-        const float l = gray_u8(r, g, b);
-        r = blend_u8(r, l, param, one_minus); g = blend_u8(g, l, param, one_minus); b = blend_u8(b, l, param, one_minus);
-    } else if (kind == kDistGamma) {
-        r = to_u8(fminf(fmaxf(powf(r / 255.f, param), 0.f), 1.f));
-        g = to_u8(fminf(fmaxf(powf(g / 255.f, param), 0.f), 1.f));
-        b = to_u8(fminf(fmaxf(powf(b / 255.f, param), 0.f), 1.f));
-    } else if (kind == kDistHue) {
-        r /= 255.f; g /= 255.f; b /= 255.f;
-        // _rgb2hsv
-        const float maxc = fmaxf(fmaxf(r, g), b), minc = fminf(fminf(r, g), b);
-        const bool eqc = maxc == minc;
-        const float cr = maxc - minc;
-        const float s = cr / (eqc ? 1.f : maxc);
-        const float div = eqc ? 1.f : cr;
-        const float rc = (maxc - r) / div, gc = (maxc - g) / div, bc = (maxc - b) / div;
-        const float hr = (maxc == r) ? (bc - gc) : 0.f;
-        const float hg = ((maxc == g) && (maxc != r)) ? (2.0f + rc - bc) : 0.f;
-        const float hb = ((maxc != g) && (maxc != r)) ? (4.0f + gc - rc) : 0.f;
-        float h = fmodf((hr + hg + hb) / 6.0f + 1.0f, 1.0f);
-        // h = (h + hue_factor) % 1.0  (python / torch remainder: result has the sign of the divisor)
-        h = h + param;
-        h = h - floorf(h);
-        // _hsv2rgb
-        const float v = maxc;
-        const float h6 = h * 6.0f;
-        const float fi = floorf(h6);
-        const float f = h6 - fi;
-        int idx = (int)fi % 6;
-        idx = idx < 0 ? idx + 6 : idx;
-        const float p = fminf(fmaxf(v * (1.0f - s), 0.f), 1.f);
-        const float q = fminf(fmaxf(v * (1.0f - (s * f)), 0.f), 1.f);
-        const float t = fminf(fmaxf(v * (1.0f - (s * (1.0f - f))), 0.f), 1.f);
-        // rows of the reference's selection tensors: (v,q,p,p,t,v), (t,v,v,q,p,p), (p,p,t,v,v,q) indexed by idx
-        r = to_u8(idx == 0 || idx == 5 ? v : idx == 1 ? q : idx == 4 ? t : p);
-        g = to_u8(idx == 1 || idx == 2 ? v : idx == 0 ? t : idx == 3 ? q : p);
-        b = to_u8(idx == 3 || idx == 4 ? v : idx == 2 ? t : idx == 5 ? q : p);
-    }
+    const float mean = kind == kDistContrast ? gray_mean(gray_sum[0], n) : 0.f;
+    distort_pixel(kind, param, one_minus, mean, r, g, b);
     if (out_u8) { out_u8[i] = (uint8_t)r; out_u8[n + i] = (uint8_t)g; out_u8[2 * n + i] = (uint8_t)b; }
     if (out_f32) { out_f32[i] = r / 255.f; out_f32[n + i] = g / 255.f; out_f32[2 * n + i] = b / 255.f; }
 }

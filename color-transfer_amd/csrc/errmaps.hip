@@ -14,11 +14,10 @@
 #include "ct_color.h"
 #include "ct_common.h"
 #include "ct_minmax.h"
+#include "ct_ssim_map.h"
 
 namespace ct {
 namespace em {
-
-typedef float vf4 __attribute__((ext_vector_type(4)));
 
 // ---- SSIM map ---------------------------------------------------------------------------------------------------------------------
 // One workgroup per 64 x 32 output tile of one frame, the three channels one after the other:
@@ -34,41 +33,6 @@ typedef float vf4 __attribute__((ext_vector_type(4)));
 // than the 64 KB a static array may have (dynamic LDS, raised once per device), and two workgroups = 8 waves per CU in its
 // 160 KB.  A 32 x 32 tile would stay under 64 KB with three workgroups per CU, but loads 1.72 pixels per output pixel instead of
 // 1.52 and runs the row pass over 1.31 rows per output row in tiles half as wide for the column pass's 8-row strips.
-constexpr int kTW = 64, kTH = 32, kRad = 5, kTaps = 2 * kRad + 1;
-constexpr int kLeft = 8;                                    // staged columns left of the tile: kRad rounded up to 16 bytes
-constexpr int kSW = kTW + 2 * kLeft, kSH = kTH + 2 * kRad;  // 80 x 42 staged pixels
-constexpr int kStrip = 8;                                   // output rows per thread in the column pass: kBlock = kTW * kTH / kStrip
-constexpr int kSsimLds = (2 * kSH * kSW + 5 * kSH * kTW + 8) * (int)sizeof(float);
-static_assert(kTW * kTH / kStrip == kBlock && kTW == kWave, "a wave owns one 8-row strip of the tile's 64 columns");
-static_assert(kSsimLds <= 80 * 1024, "two workgroups per CU");
-
-struct Taps {
-    float v[kTaps];                                         // exp(-k^2 / (2 * 1.5^2)), k = -5 .. 5, normalised: made in float64 on the host
-};
-
-// rows oy - 5 .. oy + 36, columns ox - 8 .. ox + 71 of one plane; what no output of the frame needs (beyond 5 pixels outside the
-// frame, where the reflected index would leave it again) is zero and is never read for a stored value
-__device__ __forceinline__ void stage_plane(const float *__restrict__ p, float *__restrict__ s, int H, int W, int oy, int ox, bool vec) {
-    for (int i = threadIdx.x; i < kSH * (kSW / 4); i += kBlock) {
-        const int r = i / (kSW / 4), q = i - r * (kSW / 4);
-        const int gy = oy + r - kRad, gx0 = ox - kLeft + 4 * q;
-        vf4 v = (vf4)(0.0f);
-        if (gy >= -kRad && gy < H + kRad) {
-            const float *row = p + (int64_t)reflect(gy, H) * W;
-            if (vec && gx0 >= 0 && gx0 + 3 < W) {
-                v = *reinterpret_cast<const vf4 *>(row + gx0);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int gx = gx0 + e;
-                    if (gx >= -kRad && gx < W + kRad) v[e] = row[reflect(gx, W)];
-                }
-            }
-        }
-        *reinterpret_cast<vf4 *>(s + r * kSW + 4 * q) = v;
-    }
-}
-
 __global__ __launch_bounds__(kBlock) void ssim_map_kernel(const float *__restrict__ x, const float *__restrict__ y, float *__restrict__ out, int n,
                                                           int H, int W, int vec, Taps taps, unsigned int *__restrict__ keys) {
     extern __shared__ vf4 em_smem[];                        // 16-byte aligned base
@@ -76,7 +40,6 @@ __global__ __launch_bounds__(kBlock) void ssim_map_kernel(const float *__restric
     const int ox = blockIdx.x * kTW, oy = blockIdx.y * kTH;
     const int64_t plane = (int64_t)H * W;
     const int col = threadIdx.x & (kTW - 1), r0 = (threadIdx.x >> 6) * kStrip;
-    const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
     for (int b = blockIdx.z; b < n; b += gridDim.z) {
         float sum[kStrip];                                  // the channels' SSIM values, added in their order
         for (int ch = 0; ch < 3; ++ch) {
@@ -84,47 +47,12 @@ __global__ __launch_bounds__(kBlock) void ssim_map_kernel(const float *__restric
             stage_plane(x + off, sx, H, W, oy, ox, vec);
             stage_plane(y + off, sy, H, W, oy, ox, vec);
             __syncthreads();                                // also: the previous channel's column pass has left hb
-            for (int i = threadIdx.x; i < kSH * kTW; i += kBlock) {
-                const int r = i / kTW, c = i - r * kTW;
-                const float *px = sx + r * kSW + c + (kLeft - kRad), *py = sy + r * kSW + c + (kLeft - kRad);
-                float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < kTaps; ++k) {
-                    const float a = px[k], d = py[k], g = taps.v[k];
-                    m[0] = fmaf(g, a, m[0]); m[1] = fmaf(g, d, m[1]); m[2] = fmaf(g, a * a, m[2]); m[3] = fmaf(g, d * d, m[3]); m[4] = fmaf(g, a * d, m[4]);
-                }
-#pragma unroll
-                for (int q = 0; q < 5; ++q) hb[(q * kSH + r) * kTW + c] = m[q];
-            }
+            ssim_rows(sx, sy, hb, taps);
             __syncthreads();                                // the next channel may overwrite sx / sy from here on
-            float acc[kStrip][5];
+            float v[kStrip];
+            ssim_columns(hb, taps, r0, col, v);
 #pragma unroll
-            for (int j = 0; j < kStrip; ++j)
-#pragma unroll
-                for (int q = 0; q < 5; ++q) acc[j][q] = 0.f;
-#pragma unroll
-            for (int k = 0; k < kStrip + 2 * kRad; ++k) {
-                float v[5];
-#pragma unroll
-                for (int q = 0; q < 5; ++q) v[q] = hb[(q * kSH + r0 + k) * kTW + col];
-#pragma unroll
-                for (int j = 0; j < kStrip; ++j) {
-                    if (k - j >= 0 && k - j < kTaps) {
-#pragma unroll
-                        for (int q = 0; q < 5; ++q) acc[j][q] = fmaf(taps.v[k - j], v[q], acc[j][q]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < kStrip; ++j) {
-                const float mu1 = acc[j][0], mu2 = acc[j][1];
-                const float mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
-                const float s11 = acc[j][2] - mu11, s22 = acc[j][3] - mu22, s12 = acc[j][4] - mu12;
-                const float num = (2.0f * mu12 + c1) * (2.0f * s12 + c2);
-                const float den = (mu11 + mu22 + c1) * (s11 + s22 + c2);
-                const float v = num / (den + 1e-12f);
-                sum[j] = ch == 0 ? v : sum[j] + v;
-            }
+            for (int j = 0; j < kStrip; ++j) sum[j] = ch == 0 ? v[j] : sum[j] + v[j];
         }
         float lo = __builtin_inff(), hi = -__builtin_inff();
         const int gx = ox + col;
@@ -251,10 +179,7 @@ int ct_view_ssim_map_f32(const float *x, const float *y, float *out, void *ws, s
     hipStream_t s = (hipStream_t)stream;
     static ct::DynLdsAttr attr;
     if (attr.ensure(reinterpret_cast<const void *>(ssim_map_kernel), kSsimLds) != hipSuccess) return CT_E_BADARG;
-    Taps taps;
-    double g[kTaps], sum = 0.0;
-    for (int k = 0; k < kTaps; ++k) { g[k] = __builtin_exp(-(double)((k - kRad) * (k - kRad)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
-    for (int k = 0; k < kTaps; ++k) taps.v[k] = (float)(g[k] / sum);
+    const Taps taps = ssim_taps();
     const int64_t plane = (int64_t)h * w;
     // every row of every plane starts on 16 bytes when the bases do and the width is a whole number of them
     const int vec = w % 4 == 0 && on16(x) && on16(y);

@@ -224,3 +224,12 @@ class DCMCS3DI(torch.nn.Module):
         low = ct_hip.bicubic_resize(both, scale_factor=scale_factor, antialias=antialias)
         corrected, (_, _, (valid_left, _), _) = self.forward(low[:B], low[B:], inference=True)
         return ct_hip.bicubic_resize(corrected, size=(H, W), antialias=antialias), valid_left
+
+    VALIDATION_MISSING = ("Photometric Loss", "Cycle Loss", "Smoothness Loss")     # utils.cli validate refuses before the first frame
+
+    def validation_step(self, batch, batch_idx=0, dataloader_idx=0):
+        """dcmcs3di.py:61-92 logs six losses per batch; the three PAM losses among them are not implemented here, and a validation
+        that reported a `loss` without them would not be the reference's"""
+        raise NotImplementedError("DCMCS3DI.validation_step lacks the three PAM losses of the reference's step (%s: "
+                                  "loss_pam_photometric, loss_pam_cycle, loss_pam_smoothness); methods.dmsct.DMSCT validates"
+                                  % ", ".join(DCMCS3DI.VALIDATION_MISSING))

@@ -144,3 +144,23 @@ class DMSCT(torch.nn.Module):
         result = self(batch["target"], batch["reference"])
         gt = batch["gt"].to(result.device)
         return {"Test PSNR": psnr(result, gt), "Test SSIM": ssim(result, gt), "Test FSIM": fsim(result, gt), "Test iCID": icid(result, gt)}
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0, dataloader_idx=0):
+        """dmsct.py:118-131,136-137 (`step(batch, "Validation")`): what the reference logs for one batch, under its names without the
+        prefix -- the two step losses (ct_hip.frame_losses; the 0.1 of the SSIM loss applied), the four metrics as their batch means,
+        and `loss` = MSE Loss + SSIM Loss, the value step() returns.  float64 scalars on the device; eval mode, no grad."""
+        from methods import fsim, icid, psnr, ssim
+        training = self.training
+        self.eval()
+        try:
+            result = self(batch["target"], batch["reference"]).float().contiguous()
+        finally:
+            self.train(training)
+        gt = batch["gt"].to(result.device).float().contiguous()
+        losses, _ = ct_hip.frame_losses(result, gt)
+        out = {"MSE Loss": losses[1], "SSIM Loss": 0.1 * losses[2]}
+        for name, fn in (("PSNR", psnr), ("SSIM", ssim), ("FSIM", fsim), ("iCID", icid)):
+            out[name] = fn(result, gt).mean()
+        out["loss"] = out["MSE Loss"] + out["SSIM Loss"]
+        return out

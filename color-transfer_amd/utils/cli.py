@@ -1,6 +1,7 @@
 """`python -m utils.cli test --config <yaml> [--model.func_spec ...] [--data.n_frames N] [--ckpt_path P]`
 `python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--views a,b,c] [--writer.depth D] [--writer.workers N] [--writer.png_encoder host|device] [...]`
 both with `[--inference.scale_factor S] [--inference.antialias B]`
+`python -m utils.cli validate --config <yaml> [--ckpt_path P] [--data.synthetic trainval] [--data.crop_size [H,W]] [--data.image_repeats R] [--data.batch_size B] [--seed_everything N]`
 
 A minimal look-alike of the reference's LightningCLI entry point (utils/cli.py:1-3, README.md:69-71) for the
 `test` and `predict` sub-commands (Lightning/jsonargparse are not part of this stack): YAML with `class_path/init_args`
@@ -22,6 +23,16 @@ before the first frame.  Not with `--format raw` (one file) and not with the `in
 `inference` (optional section, `inference: {scale_factor: 0.75, antialias: false}` or `--inference.scale_factor 0.75`): the model runs
 at a reduced size through its `forward_scaled` -- bicubic down, forward, bicubic back up, the reference's demo notebook, cell 24 -- and
 metrics / frames are those of the full-size result.  A model without `forward_scaled` is refused.  Without the section nothing changes.
+
+`validate`: the reference's validation epoch (`validation_step` over the two loaders of DataModule.val_dataloader(): random crops of
+the artificial validation set in batches of data.batch_size -- crop, flips and the chain of colour adjustments of a whole batch in
+one ct_hip.augment_u8 call -- and the real-world set frame by frame).  Per loader, rank 0 prints what the model's validation_step
+returns (methods.dmsct.DMSCT: MSE Loss, SSIM Loss, PSNR, SSIM, FSIM, iCID, loss) as `Validation <name>/dataloader_idx_<i>`: the mean
+over samples, every batch weighted by its size, as Lightning reduces an epoch.  Samples are sharded like frames (sample f -> rank
+f % world; a rank batches its own samples), one collective per loader.  `seed_everything: N` seeds numpy's and torch's global
+generators, from which the dataset draws, before the first loader.  The `inference` section is not used.  A model without
+`validation_step` (Runner: the reference has none), one that lacks losses (DCMCS3DI) and CT_CLI_DEVICE=cpu are refused before the
+first frame.
 
 `predict --writer.png_encoder device` (with `--format png`, the default): the PNG files are compressed on the GPU -- row filters and
 a Huffman code per 16 rows (ct_hip.png_deflate, csrc/png.hip), one launch per group of frames or per view -- and the writer's threads
@@ -152,8 +163,35 @@ def _parse(argv):
     return cfg, ckpt, opts
 
 
-def _setup(cfg, ckpt):
-    """what `test` and `predict` share: rank / device selection, the process group, the model (+ checkpoint) and the loaders"""
+def _model_class(cfg):
+    module, cls = cfg["model"]["class_path"].rsplit(".", 1)
+    return getattr(importlib.import_module(module), cls)
+
+
+VALIDATION = ("MSE Loss", "SSIM Loss", "PSNR", "SSIM", "FSIM", "iCID", "loss")      # what a validation_step returns, in the reference's order
+
+
+def _check_validate(cfg):
+    """before anything touches a device: `validate` needs a GPU and a model class with a complete validation_step"""
+    if "class_path" not in (cfg.get("model") or {}):
+        raise SystemExit("validate needs `--config <yaml>` with a `model` section (class_path / init_args), like `test` and `predict`")
+    if os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
+        raise SystemExit("validate needs a GPU: the samples are made and the losses computed on the device (ct_hip.augment_u8, "
+                         "ct_hip.frame_losses); there is no CT_CLI_DEVICE=cpu stand-in")
+    if "inference" in cfg:
+        raise SystemExit("validate does not use the `inference` section (the reference validates at the size of its crops)")
+    cls = _model_class(cfg)
+    if not hasattr(cls, "validation_step"):
+        raise SystemExit("validate needs a model with `validation_step`; %s has none (the reference's Runner has none either; "
+                         "methods.dmsct.DMSCT does)" % cls.__name__)
+    missing = getattr(cls, "VALIDATION_MISSING", ())
+    if missing:
+        raise SystemExit("validate: %s.validation_step lacks %s of the reference's step; methods.dmsct.DMSCT validates"
+                         % (cls.__name__, ", ".join(missing)))
+
+
+def _setup(cfg, ckpt, validate=False):
+    """what the sub-commands share: rank / device selection, the process group, the model (+ checkpoint) and the loaders"""
     import torch.distributed as dist
     from utils import sharding as sh
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -193,7 +231,7 @@ def _setup(cfg, ckpt):
     data_cfg = dict(cfg.get("data", {}))
     data_cfg["class_path"] = "utils.data.DataModule"
     dm = _instantiate(data_cfg)
-    loaders = dm.test_dataloader()
+    loaders = dm.val_dataloader() if validate else dm.test_dataloader()
 
     def fence():
         if world > 1:
@@ -206,15 +244,18 @@ def _setup(cfg, ckpt):
 
 
 def main(argv=None, timing=None):
-    """`test` returns the [n_frames, 4] metric table of the first loader, `predict` the number of frames written.
+    """`test` returns the [n_frames, 4] metric table of the first loader, `predict` the number of frames written, `validate` the list
+    of its loaders' [n_samples, 7] tables (cli.VALIDATION; a sample's row holds the values of its batch).
     timing: None, or a dict that receives {"seconds", "frames", "frames_local", "h2d_bytes"} of the first loader's loop --
     barrier + synchronize on both sides, the gather inside, an untimed first pass over a few groups before it (code objects,
     clocks, the communicator) -- for bench.py's configs[4] leg, which measures THIS entry point rather than a loop of its own.
     `predict` fills it the same way (+ "d2h_bytes"), the writer's drain inside the measurement."""
     argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] not in ("test", "predict"):
-        raise SystemExit("only the `test` and `predict` sub-commands exist here (fit/validate are Lightning training paths)")
+    if not argv or argv[0] not in ("test", "predict", "validate"):
+        raise SystemExit("only the `test`, `predict` and `validate` sub-commands exist here (fit is Lightning's training path)")
     cfg, ckpt, opts = _parse(argv)
+    if argv[0] == "validate":
+        _check_validate(cfg)
     if argv[0] == "predict":
         from utils.writer import FORMATS
         if not opts.get("output"):
@@ -229,9 +270,11 @@ def main(argv=None, timing=None):
         if encoder == "device" and os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
             raise SystemExit("--writer.png_encoder device needs a GPU: under CT_CLI_DEVICE=cpu the frames are host tensors and there "
                              "is no device to encode on; use the default `host` encoder")
-    ctx = _setup(cfg, ckpt)
+    ctx = _setup(cfg, ckpt, validate=argv[0] == "validate")
     import torch.distributed as dist
     try:
+        if argv[0] == "validate":
+            return _validate(ctx, cfg.get("seed_everything"))
         if argv[0] == "predict":
             if views:
                 _check_views(ctx, views)
@@ -314,6 +357,31 @@ def _test(ctx, timing):
                 print("%s%s: %.4f" % (name, suffix, float(table[:, i].mean())), end="   " if j + 1 < len(cols) else "")
             print("  (%d frames, %d GPU%s)" % (len(frames), world, "" if world == 1 else "s"))
     return tables[0]
+
+
+def _validate(ctx, seed):
+    from utils import sharding as sh
+    rank, world, device, model = ctx.rank, ctx.world, ctx.device, ctx.model
+    if seed is not None:                                    # the generators the dataset draws from (utils/data.py: sample_params)
+        import numpy as np
+        np.random.seed(int(seed))
+        torch.manual_seed(int(seed))
+    tables = []
+    for li, loader in enumerate(ctx.loaders):
+        mine = sh.frames_of_rank(len(loader), rank, world)
+        rows = []
+        for n, (ids, batch) in enumerate(loader.batches(mine, device)):
+            m = model.validation_step(batch, n, li)
+            # every sample carries the values of its batch: the mean over samples weights the batches by their size (Lightning's epoch mean)
+            rows.append(torch.stack([m[k].reshape(()).double() for k in VALIDATION]).expand(len(ids), -1))
+        local = torch.cat(rows) if rows else torch.zeros((0, len(VALIDATION)), dtype=torch.float64, device=device)
+        table = sh.gather_frame_metrics(local, len(loader), rank, world)
+        tables.append(table)
+        if rank == 0:
+            for j, name in enumerate(VALIDATION):
+                print("Validation %s/dataloader_idx_%d: %.4f" % (name, li, float(table[:, j].mean())), end="   " if j + 1 < len(VALIDATION) else "")
+            print("  (%d samples, %d GPU%s)" % (len(loader), world, "" if world == 1 else "s"))
+    return tables
 
 
 def _predict(ctx, output, fmt, writer_cfg, timing, views=None):

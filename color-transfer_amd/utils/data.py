@@ -8,6 +8,10 @@
   `*/*_LD.*`); PNG decoding stays on the host (PIL here, libpng behind torchvision.io.read_image there).
 * `SyntheticArtificialTest` / `SyntheticStereoFrames` -- stand-ins when the Kaggle / MSU datasets are not on disk (they are not
   available offline): synthetic uint8 stereo pairs through the same 31 distortions, or a synthetic float video.
+* `ArtificialTrainValDataset(image_dir, crop_size, image_repeats)` / `SyntheticTrainVal` -- the training / validation set
+  (utils/data.py:25-84): `sample_params` draws the crop corner, the two flips, the order and the strengths of the six adjustments on
+  the host, in the reference's order from the reference's generators; ct_augment_u8 applies them, a whole batch per call
+  (`BatchLoader`, `DataModule.val_dataloader()`).
 * `prefetch(dataset, indices, device)` -- yields device-resident samples while the next one is decoded into PINNED host
   memory and uploaded on a second stream (double buffer), so that the transfer kernels never wait for PCIe.
 Seeds are derived from the FRAME index (world-size independent)."""
@@ -125,6 +129,121 @@ class RealWorldTestDataset:                                   # utils/data.py:12
     def __getitem__(self, index):
         host, _ = self.host_frames(index)
         return self.finish({k: v.cuda() for k, v in host.items()}, None)
+
+
+class _TrainVal:
+    """common part of the training / validation sets (utils/data.py:52-84): sample index -> image index // image_repeats, a random
+    crop, the two flips and a random chain of the six adjustments, all drawn on the host and APPLIED on the GPU (ct_augment_u8)"""
+    # apply_uniform_distortions' fn_id -> the operation (utils/data.py:35-47)
+    OPS = ("brightness", "contrast", "saturation", "hue", "gamma", "sharpness")
+
+    def __init__(self, crop_size, image_repeats):
+        self.crop_size = (int(crop_size[-2]), int(crop_size[-1]))
+        self.image_repeats = int(image_repeats)
+
+    def __len__(self):
+        return self.n_images() * self.image_repeats
+
+    def sample_params(self, index, max_magnitude=0.5):
+        """The random draws of sample `index`, in the reference's order from the reference's generators (utils/data.py:69-80,
+        26-33): numpy's global generator for the corner (top, then left; a source no larger than the crop raises numpy's own
+        ValueError), the two flips and the six strengths (brightness, contrast, saturation, hue, gamma, sharpness), torch's
+        global generator for the order in between.  Seeding both reproduces the reference's samples in a single process."""
+        height, width = self.source_size(index // self.image_repeats)
+        top = np.random.randint(0, height - self.crop_size[0])
+        left = np.random.randint(0, width - self.crop_size[1])
+        swap_hflip = np.random.random() > 0.5
+        vflip = np.random.random() > 0.5
+        order = torch.randperm(6).tolist()
+        lo, hi = 1 - max_magnitude, 1 + max_magnitude
+        strength = [np.random.uniform(lo, hi), np.random.uniform(lo, hi), np.random.uniform(lo, hi),
+                    np.random.uniform(-max_magnitude, max_magnitude), np.random.uniform(lo, hi), np.random.uniform(lo, hi)]
+        return {"top": int(top), "left": int(left), "swap_hflip": bool(swap_hflip), "vflip": bool(vflip),
+                "ops": [(self.OPS[i], float(strength[i])) for i in order]}
+
+    def host_frames(self, index):
+        """uint8 CHW (gt, reference) of sample `index` on the host + its draws"""
+        gt, reference = self.load_pair(index // self.image_repeats)
+        return {"gt": gt, "reference": reference}, self.sample_params(index)
+
+    def finish(self, dev_u8, params):
+        """device uint8 frames [3,H,W] (one sample, params a dict) or [n,3,H,W] (a batch, params a list) -> the reference's sample
+        dict (utils/data.py:84) of that shape: ONE ct_hip.augment_u8 call either way"""
+        import ct_hip
+        single = isinstance(params, dict)
+        gt, reference = dev_u8["gt"], dev_u8["reference"]
+        out = ct_hip.augment_u8((gt[None] if single else gt).contiguous(), (reference[None] if single else reference).contiguous(),
+                                [params] if single else params, self.crop_size)
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def __getitem__(self, index):
+        host, params = self.host_frames(index)
+        return self.finish({k: v.cuda() for k, v in host.items()}, params)
+
+
+class ArtificialTrainValDataset(_TrainVal):                   # utils/data.py:52-84
+    def __init__(self, image_dir, crop_size, image_repeats):
+        super().__init__(crop_size, image_repeats)
+        image_dir = Path(image_dir)
+        self.gts = sorted(image_dir.glob("*_L.*"))
+        self.references = sorted(image_dir.glob("*_R.*"))
+        assert len(self.gts) == len(self.references)
+
+    def n_images(self):
+        return len(self.gts)
+
+    def source_size(self, i):
+        from PIL import Image
+        with Image.open(str(self.gts[i])) as im:              # the header only
+            return im.height, im.width
+
+    def load_pair(self, i):
+        return read_image(str(self.gts[i])), read_image(str(self.references[i]))
+
+
+class SyntheticTrainVal(_TrainVal):
+    """SyntheticArtificialTest's uint8 stereo pairs through the training / validation augmentation, for offline runs"""
+
+    def __init__(self, n_images=2, height=270, width=480, crop_size=(256, 448), image_repeats=1):
+        super().__init__(crop_size, image_repeats)
+        self._pairs = SyntheticArtificialTest(n_images, height, width)
+
+    def n_images(self):
+        return self._pairs.n_images()
+
+    def source_size(self, i):
+        return self._pairs.height, self._pairs.width
+
+    def load_pair(self, i):
+        return self._pairs.load_pair(i)
+
+
+class BatchLoader:
+    """What `validate` iterates: the samples of `dataset` in batches of `batch_size` consecutive samples of the caller's index list.
+    batches(indices, device) yields (the batch's sample indices, {target, reference, gt}: float32 [B,3,h,w] on the device).  A
+    training / validation set is batched BEFORE the GPU work: the uint8 sources are stacked and one ct_hip.augment_u8 call makes
+    the batch (its sources must have one size); any other dataset yields its samples one by one through `prefetch`."""
+
+    def __init__(self, dataset, batch_size=1, name="loader"):
+        self.dataset, self.batch_size, self.name = dataset, max(int(batch_size or 1), 1), name
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def batches(self, indices, device):
+        indices = list(indices)
+        if not isinstance(self.dataset, _TrainVal):
+            for index, sample in prefetch(self.dataset, indices, device):
+                yield [index], {k: v.unsqueeze(0) for k, v in sample.items()}
+            return
+        for c in range(0, len(indices), self.batch_size):
+            ids = indices[c:c + self.batch_size]
+            hosts, params = zip(*(self.dataset.host_frames(i) for i in ids))
+            if len({h["gt"].shape for h in hosts}) > 1:
+                raise ValueError("a batch is made by one augment_u8 call: its source pairs need one size (got %s)"
+                                 % sorted({tuple(h["gt"].shape) for h in hosts}))
+            dev = {k: torch.stack([h[k] for h in hosts]).to(device) for k in ("gt", "reference")}
+            yield ids, self.dataset.finish(dev, list(params))
 
 
 class SyntheticStereoFrames:
@@ -300,11 +419,17 @@ class DataModule:
     """Accepts the reference's init_args (data_dir, num_workers, crop_size, ...).  `test_frames()` = the reference's first test
     loader (ArtificialTestDataset over data_dir / "Test") when that directory exists; otherwise a synthetic stand-in:
     `synthetic: video` (default, n_frames float frames), `synthetic: artificial` (n_frames uint8 pairs x 31 distortions) or
-    `synthetic: video_u8` (n_frames uint8 frames in pinned groups of `group` = 8: configs[4])."""
+    `synthetic: video_u8` (n_frames uint8 frames in pinned groups of `group` = 8: configs[4]).
+    `val_dataloader()` = the reference's two validation loaders (utils/data.py:150-166): ArtificialTrainValDataset over data_dir /
+    "Validation" in batches of `batch_size`, and the real-world set one frame per batch; without those directories `synthetic:
+    trainval` stands in (n_frames uint8 pairs x image_repeats crops; n_frames float frames for the real-world loader).  `crop_size`,
+    `image_repeats` and `batch_size` are read by that path only."""
 
     def __init__(self, data_dir=None, num_workers=0, crop_size=None, image_repeats=None, batch_size=None,
                  n_frames=8, height=270, width=480, synthetic="video", group=8, **_):
         self.data_dir = Path(data_dir) if data_dir else None
+        self.crop_size, self.image_repeats, self.batch_size = crop_size, image_repeats, batch_size
+        self._synthetic = (synthetic, n_frames, height, width)
         if self.data_dir is not None and (self.data_dir / "Test").is_dir():
             self.dataset = ArtificialTestDataset(self.data_dir / "Test")
         elif synthetic == "artificial":
@@ -323,3 +448,22 @@ class DataModule:
         if self.data_dir is not None and (self.data_dir / "Real-World Test").is_dir():
             loaders.append(RealWorldTestDataset(self.data_dir / "Real-World Test"))
         return loaders
+
+    def val_dataloader(self):
+        """[artificial, real-world] like utils/data.py:150-166, as BatchLoaders"""
+        synthetic, n_frames, height, width = self._synthetic
+        if self.crop_size is None:
+            raise ValueError("val_dataloader needs data.crop_size (and takes data.image_repeats, data.batch_size)")
+        repeats = 1 if self.image_repeats is None else self.image_repeats
+        if self.data_dir is not None and (self.data_dir / "Validation").is_dir():
+            artificial = ArtificialTrainValDataset(self.data_dir / "Validation", self.crop_size, repeats)
+        elif synthetic == "trainval":
+            artificial = SyntheticTrainVal(n_frames, height, width, self.crop_size, repeats)
+        else:
+            raise ValueError("no %s directory: `data.synthetic: trainval` makes a synthetic validation set"
+                             % (self.data_dir / "Validation" if self.data_dir is not None else "data_dir / Validation"))
+        if self.data_dir is not None and (self.data_dir / "Real-World Test").is_dir():
+            real = RealWorldTestDataset(self.data_dir / "Real-World Test")
+        else:
+            real = SyntheticStereoFrames(n_frames, height, width)
+        return [BatchLoader(artificial, self.batch_size, "artificial"), BatchLoader(real, 1, "real-world")]

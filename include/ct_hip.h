@@ -647,6 +647,53 @@ long long ct_png_slot_capacity(int h, int w, int rows_per_chunk);
 int ct_png_deflate_u8(const uint8_t *frames, int n, int h, int w, int rows_per_chunk, uint8_t *streams, long long capacity,
                       int *sizes, unsigned int *adler, void *stream);
 
+/* ---- training / validation samples (utils/data.py:25-84: ArtificialTrainValDataset.__getitem__ + apply_uniform_distortions),
+ * csrc/augment.hip.  Entries added under ABI 9 (no argument list changed).  One call makes a batch of n samples from n source
+ * pairs gt, ref: uint8 [n][3][height][width].  Per sample (ct_augment_sample):
+ *   crop both views at (top, left) to crop_h x crop_w; swap_hflip: the new gt is the mirrored crop of ref and the new ref the
+ *   mirrored crop of gt; vflip: both upside down; target = the chain kind[0 .. n_ops - 1] applied to the new gt.
+ *   kind 0 .. 5 and their parameters as for ct_distort_u8 (the same device functions); 6 = torchvision's adjust_sharpness
+ *   (param = factor >= 0): the image passes unchanged when crop_h <= 2 or crop_w <= 2; else blend(img, degenerate, factor) with
+ *   degenerate = img on the one-pixel border and round_half_even(sum w x) over the 3 x 3 neighbourhood inside (w = 5/13 at the
+ *   centre, 1/13 elsewhere, float32), cast to uint8.  one_minus[i] = 1.0 - param[i], formed by the caller in float64.
+ *   Every operation works on the uint8 result of the one before it.  Contrast in position k blends with the mean grey of the
+ *   whole crop after operations 0 .. k - 1 (an exact integer sum).  A kind may appear more than once, sharpness at most once.
+ * samples: n records in HOST memory, checked before anything is launched; samples_dev: the same n records in device memory,
+ *   which the kernels read (they clamp what they index with, whatever it holds).
+ * out_gt, out_ref, out_target: float32 [n][3][crop_h][crop_w] = value / 255 (a float32 division); out_target_u8 (optional): the
+ *   uint8 target.  ws: ct_augment_workspace_bytes(n) bytes, 8-byte aligned (the grey sums).
+ * Launches: one over all samples, preceded -- only when a chain has a contrast -- by the zeroing of ws and one grey-sum launch
+ *   per contrast of the longest such chain (one for the dataset's chains).  Deterministic.
+ * CT_E_BADARG: a null pointer (out_target_u8 excepted), n, a size or a crop size < 1, more than 65535 samples, a crop that
+ *   leaves the source, a flag that is not 0 / 1, n_ops outside 0 .. 6, an unknown kind, hue outside [-0.5, 0.5], a negative (or
+ *   NaN) factor, two sharpness operations in one chain; CT_E_WORKSPACE: ws missing, misaligned or too small; CT_E_ALIGN: a float
+ *   output off 4 bytes, samples_dev off 8.                                                                                  */
+#define CT_AUGMENT_MAX_OPS 6
+#define CT_AUGMENT_SHARPNESS 6
+typedef struct {
+    int top, left, swap_hflip, vflip, n_ops;
+    int kind[CT_AUGMENT_MAX_OPS];
+    int reserved;
+    double param[CT_AUGMENT_MAX_OPS];
+    double one_minus[CT_AUGMENT_MAX_OPS];
+} ct_augment_sample;
+size_t ct_augment_workspace_bytes(int n);
+int ct_augment_u8(const uint8_t *gt, const uint8_t *ref, int n, int height, int width, const ct_augment_sample *samples,
+                  const ct_augment_sample *samples_dev, int crop_h, int crop_w, float *out_gt, float *out_ref, float *out_target,
+                  uint8_t *out_target_u8, void *ws, size_t ws_bytes, void *stream);
+
+/* ---- step losses (methods/dmsct.py:118-131, methods/dcmcs3di.py: l1_loss, mse_loss, kornia's ssim_loss(window_size=11)),
+ * csrc/losses.hip.  Entries added under ABI 9 (no argument list changed).  a (result), b (ground truth): float32
+ * [batch][3][h][w]; out: float64 [batch][3] = per frame mean |a - b|, mean (a - b)^2, mean clamp((1 - ssim_c) / 2, 0, 1) over
+ * channels and positions, ssim_c the per-channel map of ct_view_ssim_map_f32 (the same device code).  Differences and the map in
+ * float32, as torch computes them; sums in float64 in a fixed order (a tile launch and a finishing launch): deterministic.
+ * kornia's ssim_loss with reduction="mean" restated (parity unpinned).  ws: ct_frame_losses_workspace_bytes(batch, h, w) bytes,
+ * 8-byte aligned.  CT_E_BADARG: a null pointer, batch < 1 or > 65535, h < 6 or w < 6 (the reflect padding), more than two
+ * million rows; CT_E_WORKSPACE: ws missing, misaligned or too small; CT_E_ALIGN: a or b off 4 bytes.                         */
+size_t ct_frame_losses_workspace_bytes(int batch, int h, int w);
+int ct_frame_losses_f32(const float *a, const float *b, double *out, void *ws, size_t ws_bytes, int batch, int h, int w,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
