@@ -107,10 +107,15 @@ __device__ inline void m3_eig_sym(M3 s, M3 &v, double (&lam)[3]) {   // s = v di
     for (int sweep = 0; sweep < 12; ++sweep) {
         const double off = fabs(s.a[0][1]) + fabs(s.a[0][2]) + fabs(s.a[1][2]);
         if (off <= tiny) break;          // quadratic convergence: 4-5 sweeps for a 3x3
+        bool rotated = false;
         for (int p = 0; p < 2; ++p)
             for (int q = p + 1; q < 3; ++q) {
                 const double apq = s.a[p][q];
-                if (apq == 0.0) continue;
+                // the usual Jacobi threshold: an entry below the rounding of its two diagonal neighbours stays (it moves
+                // the eigenvalues by less than an ulp).  Rotating it away turns v by an arbitrary angle where two
+                // eigenvalues agree to rounding (c I plus noise) and costs f(s) several ulp; it also covers apq == 0.
+                if (fabs(apq) <= 0x1p-52 * (sqrt(fabs(s.a[p][p])) * sqrt(fabs(s.a[q][q])))) continue;
+                rotated = true;
                 const double theta = (s.a[q][q] - s.a[p][p]) / (2.0 * apq);
                 const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
                 const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
@@ -130,6 +135,7 @@ __device__ inline void m3_eig_sym(M3 s, M3 &v, double (&lam)[3]) {   // s = v di
                     v.a[k][q] = sn * vkp + c * vkq;
                 }
             }
+        if (!rotated) break;
     }
     for (int i = 0; i < 3; ++i) lam[i] = s.a[i][i];
 }
@@ -155,15 +161,19 @@ __device__ inline M3 m3_fun_sym(const M3 &s, int fn) {   // fn 0: sqrt, 1: inver
     return m3_from_eig(v, lam, fn);
 }
 
-__device__ inline M3 m3_chol(const M3 &s) {   // lower L with L L^T = s
+// lower L with L L^T = s.  semidefinite: a pivot that is exactly zero leaves its column zero (the factor of a PSD matrix; an
+// all-zero reference covariance then maps every pixel to mu_r, like the other two forms) instead of dividing 0 by 0; the
+// target's factor is inverted, so there a zero pivot stays the NaN it is.
+__device__ inline M3 m3_chol(const M3 &s, bool semidefinite) {
     M3 l;
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) l.a[i][j] = 0.0;
+    auto over = [&](double x, double d) { return semidefinite && d == 0.0 ? 0.0 : x / d; };
     l.a[0][0] = sqrt(s.a[0][0]);
-    l.a[1][0] = s.a[1][0] / l.a[0][0];
-    l.a[2][0] = s.a[2][0] / l.a[0][0];
+    l.a[1][0] = over(s.a[1][0], l.a[0][0]);
+    l.a[2][0] = over(s.a[2][0], l.a[0][0]);
     l.a[1][1] = sqrt(s.a[1][1] - l.a[1][0] * l.a[1][0]);
-    l.a[2][1] = (s.a[2][1] - l.a[2][0] * l.a[1][0]) / l.a[1][1];
+    l.a[2][1] = over(s.a[2][1] - l.a[2][0] * l.a[1][0], l.a[1][1]);
     l.a[2][2] = sqrt(s.a[2][2] - l.a[2][0] * l.a[2][0] - l.a[2][1] * l.a[2][1]);
     return l;
 }
@@ -202,7 +212,7 @@ __global__ void mk_coef_kernel(const double *__restrict__ stats_t, const double 
     } else if (mode == 1) {     // T = sqrtm(Sr) sqrtm(St)^-1                         (linear.py:112-115)
         T = m3_mul(m3_fun_sym(cr, 0), m3_fun_sym(ct_, 1));
     } else {                    // T = chol(Sr) chol(St)^-1                           (linear.py:108-111)
-        T = m3_mul(m3_chol(cr), m3_inv_lower(m3_chol(ct_)));
+        T = m3_mul(m3_chol(cr, true), m3_inv_lower(m3_chol(ct_, false)));
     }
     double *o = coef + (size_t)b * 16;
     for (int i = 0; i < 3; ++i)

@@ -202,6 +202,28 @@ def reinhard_persist(target, reference, gt=None, out=None, psnr_out=None, stats_
     return (o, psnr_out) if g is not None else o
 
 
+def _check_out(out, x, family):
+    """An `out` the caller passes is written as x.numel() elements from its first one: anything else is an error here, not an
+    out-of-bounds store.  Returns the entry's name."""
+    if out.device != x.device:
+        raise CtHipError("out is on %s, the input on %s" % (out.device, x.device))
+    if not out.is_contiguous():
+        raise CtHipError("out must be contiguous")
+    if out.numel() != x.numel():
+        raise CtHipError("out has %d elements, the input %d" % (out.numel(), x.numel()))
+    name = "ct_%s_%s_%s" % (family, _suffix(x), _suffix(out))
+    if name not in SIGNATURES:
+        raise CtHipError("no kernel for %s" % name)
+    return name
+
+
+def _check_records(t, batch, what):
+    """float64 [>= batch, 16] records (rgb_meancov statistics, affine3x3 coefficients), contiguous, on the current device"""
+    _require_cuda(t)
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != CT_RGB_STATS_STRIDE or t.shape[0] < batch:
+        raise CtHipError("%s must be float64 [B >= %d, %d], got %s %s" % (what, batch, CT_RGB_STATS_STRIDE, t.dtype, tuple(t.shape)))
+
+
 def mk(target, reference, decomposition="MK", out_dtype=torch.float64, out=None):
     """methods.linear.monge_kantorovitch_color_transfer on device tensors, B pairs per call, no host sync (ct_mk_*)."""
     x, _ = _as_batch(target)
@@ -212,9 +234,7 @@ def mk(target, reference, decomposition="MK", out_dtype=torch.float64, out=None)
     B, n = x.shape[0], x.shape[1] * x.shape[2]
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    name = "ct_mk_%s_%s" % (_suffix(x), _suffix(out))
-    if name not in SIGNATURES:
-        raise CtHipError("no kernel for %s" % name)
+    name = _check_out(out, x, "mk")
     ws = workspace(CT_WS_REINHARD, n, B, x.device)
     mode = {"MK": 0, "sqrt": 1, "cholesky": 2}[decomposition]
     check(getattr(lib(), name)(_ptr(x), _ptr(r), _ptr(out), n, B, mode, _ptr(ws), ws.numel(), _stream()))
@@ -224,8 +244,11 @@ def mk(target, reference, decomposition="MK", out_dtype=torch.float64, out=None)
 def mk_coef(stats_t, stats_r, decomposition="MK"):
     """On-device 3x3 algebra of MK (methods/linear.py:108-118): rgb_meancov records -> affine3x3 coefficient records."""
     mode = {"MK": 0, "sqrt": 1, "cholesky": 2}[decomposition]
-    _require_cuda(stats_t, stats_r)
+    _check_records(stats_t, 0, "stats_t")
     b = stats_t.shape[0]
+    _check_records(stats_r, b, "stats_r")
+    if stats_r.shape[0] != b:
+        raise CtHipError("stats_t holds %d records, stats_r %d" % (b, stats_r.shape[0]))
     coef = torch.empty((b, 16), dtype=torch.float64, device=stats_t.device)
     check(lib().ct_mk_coef_f64(_ptr(stats_t), _ptr(stats_r), mode, b, _ptr(coef), _stream()))
     return coef
@@ -235,12 +258,11 @@ def affine3x3(img, coef, out_dtype=torch.float64, out=None):
     """out = (x - mu_t) @ A + mu_r per image; coef float64 [B,16] = A[9], mu_t[3], mu_r[3], 0.
     Replaces methods/linear.py:80,122."""
     x, _ = _as_batch(img)
-    _require_cuda(x, coef)
+    _require_cuda(x)
     B, n = x.shape[0], x.shape[1] * x.shape[2]
+    _check_records(coef, B, "coef")
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    name = "ct_affine3x3_%s_%s" % (_suffix(x), _suffix(out))
-    if name not in SIGNATURES:
-        raise CtHipError("no kernel for %s" % name)
+    name = _check_out(out, x, "affine3x3")
     check(getattr(lib(), name)(_ptr(x), _ptr(coef), _ptr(out), n, B, _stream()))
     return out.view(img.shape)

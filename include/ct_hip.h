@@ -163,7 +163,12 @@ int ct_rgb_meancov_f64(const double *rgb, int64_t n_pixels, int n_images, double
  * stats_t / stats_r: records of ct_rgb_meancov; decomposition 0 "MK", 1 "sqrt", 2 "cholesky"; writes the 16-double coef
  * records ct_affine3x3_* consumes (T is applied as x @ T).  float64 Jacobi eigen-decomposition: the SPD matrix square root
  * is unique, so it equals scipy.linalg.sqrtm to rounding.  (Xiao's SVD-based matrix depends on LAPACK's sign
- * convention and is computed on the host.)                                                                            */
+ * convention and is computed on the host.)
+ * Degenerate covariances (where the reference raises from LAPACK): an all-zero TARGET covariance (a constant frame) gives a
+ * T that is NaN in all nine entries, for every decomposition (0 * inf in the inverse square root / the inverted factor), so
+ * that pair's output is NaN; an all-zero REFERENCE covariance gives T == 0 exactly (every pixel maps to mu_r); a singular
+ * but non-zero target covariance (a grey frame: rank 1) is NaN or huge, as the sign of a rounding-level eigenvalue falls.
+ * No record influences another one.                                                                                   */
 int ct_mk_coef_f64(const double *stats_t, const double *stats_r, int decomposition, int batch, double *coef,
                    void *stream);
 

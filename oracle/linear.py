@@ -82,6 +82,32 @@ def mk_matrix(target_cov, reference_cov, decomposition="MK"):
     raise ValueError("Unknown decomposition, use either 'cholesky', 'sqrt', or 'MK'")
 
 
+def mk_matrix_mp(target_cov, reference_cov, decomposition="MK", dps=60):
+    """The three closed forms of mk_matrix in mpmath at `dps` decimal digits, rounded to float64 once at the end: what the
+    float64 algebra (scipy's here, Jacobi on the device) is measured against.  The square root of a symmetric positive
+    definite matrix is V diag(sqrt(lambda)) V^T of its eigen-decomposition (unique, so it is scipy.linalg.sqrtm's)."""
+    import mpmath as mp
+
+    def sqrtm(s):
+        lam, v = mp.eigsy((s + s.T) / 2)
+        return v * mp.diag([mp.sqrt(x) for x in lam]) * v.T
+
+    with mp.workdps(dps):
+        st = mp.matrix(np.asarray(target_cov, dtype=np.float64).tolist())
+        sr = mp.matrix(np.asarray(reference_cov, dtype=np.float64).tolist())
+        if decomposition == "cholesky":
+            T = mp.cholesky(sr) * mp.inverse(mp.cholesky(st))
+        elif decomposition == "sqrt":
+            T = sqrtm(sr) * mp.inverse(sqrtm(st))
+        elif decomposition == "MK":
+            A = sqrtm(st)
+            Ainv = mp.inverse(A)
+            T = Ainv * sqrtm(A * sr * A) * Ainv
+        else:
+            raise ValueError("Unknown decomposition, use either 'cholesky', 'sqrt', or 'MK'")
+        return np.array([[float(T[i, j]) for j in range(3)] for i in range(3)], dtype=np.float64)
+
+
 def monge_kantorovitch_color_transfer(target, reference, decomposition="MK"):
     """Pitie & Kokaram 2007 (methods/linear.py:85-124). Note ``@ T`` (no transpose)."""
     shape = np.shape(target)
