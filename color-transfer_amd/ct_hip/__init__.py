@@ -39,6 +39,7 @@ from .views import (CT_VIEW_ABMSE, CT_VIEW_GRAY, CT_VIEW_LABMSE, CT_VIEW_RGBMSE,
                     rgbmse_view, rgbssim_view)
 from .png import PNG_ROWS_PER_CHUNK, png_deflate, png_geometry
 from .augment import AUGMENT_KINDS, AUGMENT_MAX_OPS, AUGMENT_SAMPLE, augment_table, augment_u8, frame_losses
+from .pam_losses import PAM_SWEEP_MAX_W, masked_l1_sums, pam_cycle_l1, pam_map_sweep
 from . import _core
 
 

@@ -7,7 +7,8 @@ ct_conv3x3_ws16_f32 (weights stationary in registers, two fp16 pieces per float3
 other convolutions in ct_conv2d_split_f32 (three bf16 pieces) -- or all of them in ct_conv2d_f32
 (exact-f32 MFMA) in `exact` mode; the parallax attention in the streaming kernels behind
 ct_hip.pam_streaming (ct_pam_attend_f32 / ct_pam_valid_f32 when the [B,H,W,W] maps are wanted); torch
-only allocates tensors.  Training (`step`, losses, logging: dcmcs3di.py:68-147) is out of scope.
+only allocates tensors.  `step(batch)` gives what the reference's step logs for a batch (dcmcs3di.py:68-92), the three
+parallax-attention losses from pasmnet.losses (csrc/pam_losses.hip), without autograd; training itself is out of scope.
 `disparity(left, right)` gives the left view's disparity of the reference's log_images (dcmcs3di.py:126,
 pasmnet/utils.py:55-105) from the streaming attention, at any width and without a [B,H,W,W] map.
 `forward_scaled(left, right, scale_factor)` is the calling convention of the reference's demo notebook (cell 24): bicubic down, the
@@ -225,11 +226,48 @@ class DCMCS3DI(torch.nn.Module):
         corrected, (_, _, (valid_left, _), _) = self.forward(low[:B], low[B:], inference=True)
         return ct_hip.bicubic_resize(corrected, size=(H, W), antialias=antialias), valid_left
 
+    @torch.no_grad()
+    def step(self, batch, prefix="Validation"):
+        """The reference's step (dcmcs3di.py:68-92) for one batch {"target", "reference", "gt"} of [B,3,H,W] device tensors: what it
+        logs, in its logging order and under its names without the prefix (as DMSCT.validation_step) -- `L1 Loss`, `MSE Loss`,
+        `SSIM Loss` (ct_hip.frame_losses; unscaled here, dcmcs3di.py:73), `Photometric Loss`, `Cycle Loss`, `Smoothness Loss` (pasmnet.losses,
+        each x 0.005), `PSNR`, `SSIM`, `FSIM`, `iCID` (batch means) -- and `loss`, the sum of the six losses that step() returns.
+        float64 scalars on the device, nothing synchronises.
+
+        The forward is the training-mode one (inference=False): forward_parts(want_att=True, want_valid_right=True), masks > 0.5.
+        The cycle loss comes from the two attention maps through the fused kernel (pasmnet.losses.loss_pam_cycle_from_att), so the
+        two cycle maps of forward()'s return value are never built.  Memory: the two [B,H,W,W] float32 attention maps (524 MB each
+        at the training crop of configs/dcmcs3di.yaml, batch 8 of 160 x 320) plus a few KB of partial sums.
+
+        Runs under no_grad: NO autograd is offered, the values are for logging and validation, not for a backward pass.  `prefix`
+        is accepted for the reference's signature and does not change the keys."""
+        from methods import fsim, icid, psnr, ssim
+        from pasmnet import losses as pam
+        left = batch["target"].contiguous().float()
+        right = batch["reference"].to(left.device).contiguous().float()
+        p = self.forward_parts(left, right, want_att=True, want_valid_right=True)
+        result = p["corrected"].float().contiguous()
+        gt = batch["gt"].to(result.device).float().contiguous()
+        att = (p["att_r2l"], p["att_l2r"])
+        valid = (p["valid_left"] > 0.5, p["valid_right"] > 0.5)
+        frame, _ = ct_hip.frame_losses(result, gt)
+        out = {"L1 Loss": frame[0], "MSE Loss": frame[1], "SSIM Loss": frame[2],
+               "Photometric Loss": 0.005 * pam.loss_pam_photometric(left, right, att, valid),
+               "Cycle Loss": 0.005 * pam.loss_pam_cycle_from_att(att, valid),
+               "Smoothness Loss": 0.005 * pam.loss_pam_smoothness(att)}
+        loss = out["L1 Loss"] + out["MSE Loss"] + out["SSIM Loss"] + out["Photometric Loss"] + out["Cycle Loss"] + out["Smoothness Loss"]
+        for name, fn in (("PSNR", psnr), ("SSIM", ssim), ("FSIM", fsim), ("iCID", icid)):
+            out[name] = fn(result, gt).mean()
+        out["loss"] = loss
+        return out
+
     VALIDATION_MISSING = ("Photometric Loss", "Cycle Loss", "Smoothness Loss")     # utils.cli validate refuses before the first frame
 
     def validation_step(self, batch, batch_idx=0, dataloader_idx=0):
-        """dcmcs3di.py:61-92 logs six losses per batch; the three PAM losses among them are not implemented here, and a validation
-        that reported a `loss` without them would not be the reference's"""
-        raise NotImplementedError("DCMCS3DI.validation_step lacks the three PAM losses of the reference's step (%s: "
-                                  "loss_pam_photometric, loss_pam_cycle, loss_pam_smoothness); methods.dmsct.DMSCT validates"
+        """dcmcs3di.py:97-98 is step(batch, "Validation").  step() above computes all of it, the three PAM losses included
+        (pasmnet.losses), but `utils.cli validate` is not wired to it yet: validation_step and VALIDATION_MISSING keep refusing until it is
+        """
+        raise NotImplementedError("DCMCS3DI.validation_step is not wired to DCMCS3DI.step yet: step(batch) returns the reference's "
+                                  "quantities, %s (pasmnet.losses: loss_pam_photometric, loss_pam_cycle, loss_pam_smoothness) "
+                                  "included, but `utils.cli validate` does not call it; methods.dmsct.DMSCT validates"
                                   % ", ".join(DCMCS3DI.VALIDATION_MISSING))

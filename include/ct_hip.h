@@ -699,6 +699,36 @@ size_t ct_frame_losses_workspace_bytes(int batch, int h, int w);
 int ct_frame_losses_f32(const float *a, const float *b, double *out, void *ws, size_t ws_bytes, int batch, int h, int w,
                         void *stream);
 
+/* ---- the parallax-attention losses of the reference's step (methods/dcmcs3di.py:68-92 through pasmnet/losses.py), csrc/pam_losses.hip.
+ * Entries added under ABI 9 (no argument list changed).  Per-image float64 SUMS and counts over materialised attention maps
+ * att [n][h][w][w] float32 (att[b][h][i][j]: query column i, key column j); mask [n][1][h][w] float32 0 / 1.  Every term is formed
+ * in float32 as the reference's torch code forms it and widened to float64 before it is added; workgroup partials in ws, added in
+ * a fixed order by a finishing launch: deterministic, no atomics.  Nothing is divided here: a zero count stays zero, and the
+ * caller's sum / count gives the reference's 0 / 0 = NaN.
+ *   ws: ct_pam_losses_workspace_bytes(n, h, w) bytes (enough for every entry below at that size), 8-byte aligned.
+ *   ct_pam_cycle_l1_f32: out [n][2] = { sum_h sum_i mask[h][i] sum_k |(A_h . B_h)[i][k] - delta_ik|, sum mask }: loss_pam_cycle's
+ *       numerator and count for the cycle map att_a . att_b, which is never stored (exact-f32 MFMA, float32 fma chain over k).
+ *   ct_pam_map_sweep_f32: out [n][5] = { sum |att[h][i][j] - att[h+1][i][j]|                     (count (h-1) w w),
+ *                                        sum |att[h][i][j] - att[h][i+1][j+1]|                   (count h (w-1) (w-1)),
+ *                                        sum_c sum_h sum_i mask[h][i] |dst[c][h][i] - sum_j att[h][i][j] src[c][h][j]|,
+ *                                        sum_h sum_i mask[h][i] sum_j |att[h][i][j] - delta_ij|,
+ *                                        sum mask }
+ *       src, dst [n][3][h][w] and mask are nullable and only switch terms off (their slots are 0): the third needs all three, the
+ *       fourth and fifth the mask.  w <= 1024.
+ *   ct_masked_l1_f32: out [n][2] = { sum |x - y| * mask, sum mask } for x, y [n][a][p][b] and mask [n][p] (broadcast over a and b):
+ *       the reference's masked_l1_loss, a = 3, b = 1 for images [n][3][h][w], a = 1, b = w for maps [n][h][w][w], p = h w.
+ *       ws: at least n * 64 * 8 bytes.
+ * CT_E_BADARG: a null pointer that is not optional, n < 1 or > 65535, a size < 1, h > 65535 (cycle), w > 1024 (sweep), src without
+ * dst or mask; CT_E_WORKSPACE: ws missing, misaligned or too small; CT_E_ALIGN: a tensor off its element size.  All before
+ * anything touches the device.                                                                                              */
+size_t ct_pam_losses_workspace_bytes(int n, int h, int w);
+int ct_pam_cycle_l1_f32(const float *att_a, const float *att_b, const float *mask, double *out, void *ws, size_t ws_bytes, int n,
+                        int h, int w, void *stream);
+int ct_pam_map_sweep_f32(const float *att, const float *src, const float *dst, const float *mask, double *out, void *ws,
+                         size_t ws_bytes, int n, int h, int w, void *stream);
+int ct_masked_l1_f32(const float *x, const float *y, const float *mask, double *out, void *ws, size_t ws_bytes, int n, int64_t a,
+                     int64_t p, int64_t b, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
