@@ -37,7 +37,7 @@ from .unet import dwconv, gconv2d_pad, scale_planes_, se_gate, upsample2_concat
 from .disparity import attention_rows64_index, pam_disp_fill, regress_disp
 from .views import (CT_VIEW_ABMSE, CT_VIEW_GRAY, CT_VIEW_LABMSE, CT_VIEW_RGBMSE, abmse_view, chess_mix, flow_to_image, gray_view, labmse_view,
                     rgbmse_view, rgbssim_view)
-from .png import PNG_ROWS_PER_CHUNK, png_deflate, png_geometry
+from .png import INFLATE_STATUS, PNG_MAX_WIDTH, PNG_ROWS_PER_CHUNK, inflate, png_decode, png_deflate, png_geometry
 from .augment import AUGMENT_KINDS, AUGMENT_MAX_OPS, AUGMENT_SAMPLE, augment_table, augment_u8, frame_losses
 from .pam_losses import PAM_SWEEP_MAX_W, masked_l1_sums, pam_cycle_l1, pam_map_sweep
 from . import _core

@@ -39,6 +39,11 @@ a Huffman code per 16 rows (ct_hip.png_deflate, csrc/png.hip), one launch per gr
 only wrap the downloaded streams into the container (utils/png.py).  The files decode to the same pixels; they are larger than the
 host encoder's (no LZ77 matching).  It goes with `--views`; under CT_CLI_DEVICE=cpu it is refused before the first frame.  The default
 is `host`: PIL on the writer's threads, as before.
+
+`--data.png_decoder device [--data.decode_ahead N]` (test, validate, predict; datasets that read PNG files): the files are inflated
+and unfiltered on the GPU (ct_hip.png_decode, csrc/png_decode.hip), N samples' files per call (default 16,
+utils.data.prefetch_decoded); what the device decoder does not take (anything but 8-bit RGB without interlace) is decoded by PIL as
+before, file by file.  Under CT_CLI_DEVICE=cpu it is refused before the first frame.  The default is `host`: nothing changes.
 """
 import importlib
 import inspect
@@ -239,8 +244,15 @@ def _setup(cfg, ckpt, validate=False):
         if not on_cpu:
             torch.cuda.synchronize()
 
+    def samples(frames, indices):
+        """(index, sample) of a loader: `prefetch`, or `prefetch_decoded` for a file dataset with --data.png_decoder device"""
+        from utils.data import prefetch, prefetch_decoded
+        if not on_cpu and getattr(frames, "png_decoder", "host") == "device":
+            return prefetch_decoded(frames, indices, device, dm.decode_ahead)
+        return prefetch(frames, indices, device)
+
     return types.SimpleNamespace(rank=rank, world=world, on_cpu=on_cpu, device=device, own_group=own_group, model=model,
-                                 loaders=loaders, fence=fence, scaled=scaled)
+                                 loaders=loaders, fence=fence, scaled=scaled, samples=samples)
 
 
 def main(argv=None, timing=None):
@@ -270,6 +282,13 @@ def main(argv=None, timing=None):
         if encoder == "device" and os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
             raise SystemExit("--writer.png_encoder device needs a GPU: under CT_CLI_DEVICE=cpu the frames are host tensors and there "
                              "is no device to encode on; use the default `host` encoder")
+    from utils.data import PNG_DECODERS
+    decoder = ((cfg.get("data") or {}).get("init_args") or {}).get("png_decoder", "host")
+    if decoder not in PNG_DECODERS:
+        raise SystemExit("--data.png_decoder %r: one of %s" % (decoder, ", ".join(PNG_DECODERS)))
+    if decoder == "device" and os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
+        raise SystemExit("--data.png_decoder device needs a GPU: under CT_CLI_DEVICE=cpu the frames are host tensors and there "
+                         "is no device to decode on; use the default `host` decoder")
     ctx = _setup(cfg, ckpt, validate=argv[0] == "validate")
     import torch.distributed as dist
     try:
@@ -289,7 +308,7 @@ def _test(ctx, timing):
     import torch.distributed as dist
     from utils import sharding as sh
     from methods import METRICS, fsim, icid, psnr, ssim
-    from utils.data import prefetch, prefetch_groups
+    from utils.data import prefetch_groups
     rank, world, on_cpu, device, model, loaders, fence = ctx.rank, ctx.world, ctx.on_cpu, ctx.device, ctx.model, ctx.loaders, ctx.fence
     # the reference's test_dataloader() returns [artificial, real-world] (utils/data.py:168-179) and Lightning logs each
     # metric once per loader ("Test PSNR/dataloader_idx_1"); a single loader prints the bare names like Lightning does
@@ -324,7 +343,7 @@ def _test(ctx, timing):
                 import time
                 t0 = time.perf_counter()
             rows = []
-            for f, sample in prefetch(frames, mine, device):       # pinned double-buffered uploads on a second stream
+            for f, sample in ctx.samples(frames, mine):            # pinned double-buffered uploads on a second stream (prefetch)
                 batch = {k: v.unsqueeze(0) for k, v in sample.items()}
                 if ctx.scaled:                          # reduced-scale inference, scored at full size like the branch below
                     corrected = model.forward_scaled(batch["target"], batch["reference"], **ctx.scaled)[0].clamp(0, 1)
@@ -388,7 +407,7 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
     import time
     import torch.distributed as dist
     from utils import sharding as sh
-    from utils.data import prefetch, prefetch_groups
+    from utils.data import prefetch_groups
     from utils.writer import FrameWriter, truncate_raw
     rank, world, on_cpu, device, model, loaders, fence = ctx.rank, ctx.world, ctx.on_cpu, ctx.device, ctx.model, ctx.loaders, ctx.fence
     depth, workers = int(writer_cfg.get("depth", 3)), int(writer_cfg.get("workers", 4))
@@ -427,7 +446,7 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
                         slot, u8 = pack(n, model.predict_group(dev), "hwc")
                         downloaded[slot] = writer.submit(ids, u8)
                     return
-                for n, (f, sample) in enumerate(prefetch(frames, indices, device)):
+                for n, (f, sample) in enumerate(ctx.samples(frames, indices)):
                     batch = {k: v.unsqueeze(0) for k, v in sample.items()}
                     if views and not on_cpu:
                         # ONE forward for the frame and all its views (freshly allocated uint8 frames: submit() holds them until

@@ -5,13 +5,17 @@
   torchvision's uint8 tensor arithmetic restated) to the uint8 ground-truth frame, index -> (image index // 31, distortion
   index % 31) exactly like the reference.
 * `ArtificialTestDataset(image_dir)` / `RealWorldTestDataset(image_dir)` -- the reference's file layouts (`*_L.*`, `*_R.*`,
-  `*/*_LD.*`); PNG decoding stays on the host (PIL here, libpng behind torchvision.io.read_image there).
+  `*/*_LD.*`); PNG decoding is on the host by default (PIL here, libpng behind torchvision.io.read_image there).
 * `SyntheticArtificialTest` / `SyntheticStereoFrames` -- stand-ins when the Kaggle / MSU datasets are not on disk (they are not
   available offline): synthetic uint8 stereo pairs through the same 31 distortions, or a synthetic float video.
 * `ArtificialTrainValDataset(image_dir, crop_size, image_repeats)` / `SyntheticTrainVal` -- the training / validation set
   (utils/data.py:25-84): `sample_params` draws the crop corner, the two flips, the order and the strengths of the six adjustments on
   the host, in the reference's order from the reference's generators; ct_augment_u8 applies them, a whole batch per call
   (`BatchLoader`, `DataModule.val_dataloader()`).
+* `png_decoder="device"` on the file datasets and `DataModule`: `host_frames` hands over each file's zlib payload instead of its
+  pixels (files that ct_hip.png_decode does not take are decoded by PIL as before) and `finish` decodes on the GPU;
+  `prefetch_decoded(dataset, indices, device, ahead)` reads `ahead` samples' files, uploads them in one copy and decodes all their
+  streams in ONE call (a stream occupies one wave: a call needs many to fill the GPU).
 * `prefetch(dataset, indices, device)` -- yields device-resident samples while the next one is decoded into PINNED host
   memory and uploaded on a second stream (double buffer), so that the transfer kernels never wait for PCIe.
 Seeds are derived from the FRAME index (world-size independent)."""
@@ -42,6 +46,65 @@ def read_image(path):
     return torch.from_numpy(np.ascontiguousarray(arr.transpose(2, 0, 1)))
 
 
+PNG_DECODERS = ("host", "device")
+
+
+def check_png_decoder(value):
+    if value not in PNG_DECODERS:
+        raise ValueError("png_decoder %r: one of %s" % (value, ", ".join(PNG_DECODERS)))
+    return value
+
+
+class Encoded:
+    """what `host_frames` hands over with png_decoder="device": the dataset's own extra and, per frame that is still a zlib
+    payload (a 1-D uint8 tensor), its (height, width); frames that PIL decoded are uint8 [3,H,W] and have no entry"""
+
+    def __init__(self, extra, dims):
+        self.extra, self.dims = extra, dims
+
+
+def read_encoded(path):
+    """(the file's zlib payload as a 1-D uint8 tensor, (height, width)) where ct_hip.png_decode takes the file -- 8-bit RGB, no
+    interlace, a sound container -- and otherwise (read_image(path), None): PIL decodes it, or raises what it raises today"""
+    from utils import png
+    from ct_hip.png import PNG_MAX_WIDTH
+    with open(path, "rb") as fh:
+        data = fh.read()
+    try:
+        info = png.parse(data)
+    except ValueError:
+        info = None
+    if info is None or not png.device_decodable(info) or info.width > PNG_MAX_WIDTH or info.height * (1 + 3 * info.width) > 0x7fffffff:
+        return read_image(path), None
+    return torch.frombuffer(bytearray(info.payload), dtype=torch.uint8), (info.height, info.width)
+
+
+def read_frames(paths, extra, png_decoder):
+    """{name: path} -> (host dict, extra) as `host_frames` returns them, for either decoder"""
+    if png_decoder != "device":
+        return {k: read_image(str(p)) for k, p in paths.items()}, extra
+    host, dims = {}, {}
+    for k, p in paths.items():
+        host[k], d = read_encoded(str(p))
+        if d is not None:
+            dims[k] = d
+    return host, Encoded(extra, dims)
+
+
+def decode_samples(samples):
+    """[(device dict, extra)] -> the same with every zlib payload decoded to uint8 [3,H,W] and the dataset's own extra back in
+    place: ONE ct_hip.png_decode call for all of them.  Samples of a host-decoder dataset pass through."""
+    todo = [(n, k) for n, (dev, extra) in enumerate(samples) if isinstance(extra, Encoded) for k in sorted(extra.dims)]
+    frames = []
+    if todo:
+        import ct_hip
+        frames = ct_hip.png_decode([(samples[n][0][k],) + tuple(samples[n][1].dims[k]) for n, k in todo])
+    out = [(dict(dev), extra.extra if isinstance(extra, Encoded) else extra) for dev, extra in samples]
+    for (n, k), frame in zip(todo, frames):
+        out[n][0][k] = frame
+    return out
+
+
 class _Distorted:
     """common part of the artificial test sets: sample index -> (image, distortion); uint8 host frames in, device floats out"""
 
@@ -60,6 +123,7 @@ class _Distorted:
     def finish(dev_u8, distortion):
         """device uint8 frames -> the reference's sample dict (utils/data.py:125): gt / 255, reference / 255, target / 255"""
         import ct_hip
+        (dev_u8, distortion), = decode_samples([(dev_u8, distortion)])
         out = {k: ct_hip.distort_u8(v.contiguous(), "identity", 0.0) for k, v in dev_u8.items()}      # x / 255 in float32
         out["target"] = ct_hip.distort_u8(dev_u8["gt"].contiguous(), distortion[0], distortion[1])
         return out
@@ -70,8 +134,9 @@ class _Distorted:
 
 
 class ArtificialTestDataset(_Distorted):                      # utils/data.py:107-125
-    def __init__(self, image_dir):
+    def __init__(self, image_dir, png_decoder="host"):
         super().__init__()
+        self.png_decoder = check_png_decoder(png_decoder)
         image_dir = Path(image_dir)
         self.gts = sorted(image_dir.glob("*_L.*"))
         self.references = sorted(image_dir.glob("*_R.*"))
@@ -82,6 +147,12 @@ class ArtificialTestDataset(_Distorted):                      # utils/data.py:10
 
     def load_pair(self, i):
         return read_image(str(self.gts[i])), read_image(str(self.references[i]))
+
+    def host_frames(self, index):
+        if self.png_decoder != "device":
+            return super().host_frames(index)
+        i, d = divmod(index, len(self.distortions))
+        return read_frames({"gt": self.gts[i], "reference": self.references[i]}, self.distortions[d], self.png_decoder)
 
 
 class SyntheticArtificialTest(_Distorted):
@@ -107,7 +178,8 @@ class SyntheticArtificialTest(_Distorted):
 
 
 class RealWorldTestDataset:                                   # utils/data.py:128-145
-    def __init__(self, image_dir):
+    def __init__(self, image_dir, png_decoder="host"):
+        self.png_decoder = check_png_decoder(png_decoder)
         image_dir = Path(image_dir)
         self.gts = sorted(image_dir.glob("*/*_L.*"))
         self.targets = sorted(image_dir.glob("*/*_LD.*"))
@@ -118,17 +190,17 @@ class RealWorldTestDataset:                                   # utils/data.py:12
         return len(self.gts)
 
     def host_frames(self, index):
-        return {"gt": read_image(str(self.gts[index])), "reference": read_image(str(self.references[index])),
-                "target": read_image(str(self.targets[index]))}, None
+        return read_frames({"gt": self.gts[index], "reference": self.references[index], "target": self.targets[index]}, None, self.png_decoder)
 
     @staticmethod
-    def finish(dev_u8, _):
+    def finish(dev_u8, extra):
         import ct_hip
+        (dev_u8, _), = decode_samples([(dev_u8, extra)])
         return {k: ct_hip.distort_u8(v.contiguous(), "identity", 0.0) for k, v in dev_u8.items()}
 
     def __getitem__(self, index):
-        host, _ = self.host_frames(index)
-        return self.finish({k: v.cuda() for k, v in host.items()}, None)
+        host, extra = self.host_frames(index)
+        return self.finish({k: v.cuda() for k, v in host.items()}, extra)
 
 
 class _TrainVal:
@@ -170,6 +242,8 @@ class _TrainVal:
         """device uint8 frames [3,H,W] (one sample, params a dict) or [n,3,H,W] (a batch, params a list) -> the reference's sample
         dict (utils/data.py:84) of that shape: ONE ct_hip.augment_u8 call either way"""
         import ct_hip
+        if isinstance(params, Encoded):
+            (dev_u8, params), = decode_samples([(dev_u8, params)])
         single = isinstance(params, dict)
         gt, reference = dev_u8["gt"], dev_u8["reference"]
         out = ct_hip.augment_u8((gt[None] if single else gt).contiguous(), (reference[None] if single else reference).contiguous(),
@@ -182,8 +256,9 @@ class _TrainVal:
 
 
 class ArtificialTrainValDataset(_TrainVal):                   # utils/data.py:52-84
-    def __init__(self, image_dir, crop_size, image_repeats):
+    def __init__(self, image_dir, crop_size, image_repeats, png_decoder="host"):
         super().__init__(crop_size, image_repeats)
+        self.png_decoder = check_png_decoder(png_decoder)
         image_dir = Path(image_dir)
         self.gts = sorted(image_dir.glob("*_L.*"))
         self.references = sorted(image_dir.glob("*_R.*"))
@@ -199,6 +274,12 @@ class ArtificialTrainValDataset(_TrainVal):                   # utils/data.py:52
 
     def load_pair(self, i):
         return read_image(str(self.gts[i])), read_image(str(self.references[i]))
+
+    def host_frames(self, index):
+        if self.png_decoder != "device":
+            return super().host_frames(index)
+        i = index // self.image_repeats
+        return read_frames({"gt": self.gts[i], "reference": self.references[i]}, self.sample_params(index), self.png_decoder)
 
 
 class SyntheticTrainVal(_TrainVal):
@@ -222,23 +303,34 @@ class BatchLoader:
     """What `validate` iterates: the samples of `dataset` in batches of `batch_size` consecutive samples of the caller's index list.
     batches(indices, device) yields (the batch's sample indices, {target, reference, gt}: float32 [B,3,h,w] on the device).  A
     training / validation set is batched BEFORE the GPU work: the uint8 sources are stacked and one ct_hip.augment_u8 call makes
-    the batch (its sources must have one size); any other dataset yields its samples one by one through `prefetch`."""
+    the batch (its sources must have one size); any other dataset yields its samples one by one through `prefetch`.  With
+    png_decoder="device" the files of a whole batch are decoded by one ct_hip.png_decode call (`prefetch_decoded` for the others)."""
 
-    def __init__(self, dataset, batch_size=1, name="loader"):
-        self.dataset, self.batch_size, self.name = dataset, max(int(batch_size or 1), 1), name
+    def __init__(self, dataset, batch_size=1, name="loader", decode_ahead=16):
+        self.dataset, self.batch_size, self.name, self.decode_ahead = dataset, max(int(batch_size or 1), 1), name, decode_ahead
 
     def __len__(self):
         return len(self.dataset)
 
     def batches(self, indices, device):
         indices = list(indices)
+        on_device = getattr(self.dataset, "png_decoder", "host") == "device"
         if not isinstance(self.dataset, _TrainVal):
-            for index, sample in prefetch(self.dataset, indices, device):
+            samples = prefetch_decoded(self.dataset, indices, device, self.decode_ahead) if on_device else prefetch(self.dataset, indices, device)
+            for index, sample in samples:
                 yield [index], {k: v.unsqueeze(0) for k, v in sample.items()}
             return
         for c in range(0, len(indices), self.batch_size):
             ids = indices[c:c + self.batch_size]
             hosts, params = zip(*(self.dataset.host_frames(i) for i in ids))
+            if on_device:                                       # the batch's files: one upload, one decode
+                decoded = decode_samples(upload_samples(list(zip(hosts, params)), device))
+                if len({d["gt"].shape for d, _ in decoded}) > 1:
+                    raise ValueError("a batch is made by one augment_u8 call: its source pairs need one size (got %s)"
+                                     % sorted({tuple(d["gt"].shape) for d, _ in decoded}))
+                dev = {k: torch.stack([d[k] for d, _ in decoded]) for k in ("gt", "reference")}
+                yield ids, self.dataset.finish(dev, [p for _, p in decoded])
+                continue
             if len({h["gt"].shape for h in hosts}) > 1:
                 raise ValueError("a batch is made by one augment_u8 call: its source pairs need one size (got %s)"
                                  % sorted({tuple(h["gt"].shape) for h in hosts}))
@@ -318,6 +410,43 @@ def prefetch(dataset, indices, device):
         for v in dev.values():
             v.record_stream(torch.cuda.current_stream(device))
         yield index, (dev if extra == "float" else dataset.finish(dev, extra))
+
+
+def upload_samples(samples, device):
+    """[(host dict of uint8 tensors, extra)] -> the same on `device`: every tensor of every sample through ONE pinned buffer and
+    one copy on the current stream (the pinned block is not reused before the copy has been made: torch's host allocator)"""
+    tensors = [v for host, _ in samples for v in host.values()]
+    total = sum(t.numel() for t in tensors)
+    pinned = torch.empty(max(total, 1), dtype=torch.uint8).pin_memory()
+    at = 0
+    for t in tensors:
+        pinned[at:at + t.numel()] = t.reshape(-1)
+        at += t.numel()
+    dev_all = pinned.to(device, non_blocking=True)
+    out, at = [], 0
+    for host, extra in samples:
+        dev = {}
+        for k, v in host.items():
+            dev[k] = dev_all[at:at + v.numel()].view(v.shape)
+            at += v.numel()
+        out.append((dev, extra))
+    return out
+
+
+def prefetch_decoded(dataset, indices, device, ahead=16):
+    """Yield (index, sample) like `prefetch`, for a dataset with png_decoder="device": the files of `ahead` samples are read and
+    parsed on the host, uploaded in one copy, ALL their zlib streams decoded by one ct_hip.png_decode call (one wave per stream: three
+    streams would use 3 of some 2000 wave slots), and the samples yielded one by one through `finish`.  A dataset with the host
+    decoder takes the same route with nothing left to decode."""
+    indices = list(indices)
+    ahead = max(int(ahead), 1)
+    if torch.device(device).type == "cpu":
+        raise ValueError("prefetch_decoded decodes on the GPU: there is no CPU path")
+    for c in range(0, len(indices), ahead):
+        ids = indices[c:c + ahead]
+        decoded = decode_samples(upload_samples([dataset.host_frames(i) for i in ids], device))
+        for index, (dev, extra) in zip(ids, decoded):
+            yield index, dataset.finish(dev, extra)
 
 
 class SyntheticStereoVideoU8:
@@ -423,15 +552,18 @@ class DataModule:
     `val_dataloader()` = the reference's two validation loaders (utils/data.py:150-166): ArtificialTrainValDataset over data_dir /
     "Validation" in batches of `batch_size`, and the real-world set one frame per batch; without those directories `synthetic:
     trainval` stands in (n_frames uint8 pairs x image_repeats crops; n_frames float frames for the real-world loader).  `crop_size`,
-    `image_repeats` and `batch_size` are read by that path only."""
+    `image_repeats` and `batch_size` are read by that path only.
+    `png_decoder`: "host" (default: PIL on the calling thread) or "device" (ct_hip.png_decode, `decode_ahead` samples per call) for
+    the datasets that read files; the synthetic ones have nothing to decode."""
 
     def __init__(self, data_dir=None, num_workers=0, crop_size=None, image_repeats=None, batch_size=None,
-                 n_frames=8, height=270, width=480, synthetic="video", group=8, **_):
+                 n_frames=8, height=270, width=480, synthetic="video", group=8, png_decoder="host", decode_ahead=16, **_):
+        self.png_decoder, self.decode_ahead = check_png_decoder(png_decoder), max(int(decode_ahead), 1)
         self.data_dir = Path(data_dir) if data_dir else None
         self.crop_size, self.image_repeats, self.batch_size = crop_size, image_repeats, batch_size
         self._synthetic = (synthetic, n_frames, height, width)
         if self.data_dir is not None and (self.data_dir / "Test").is_dir():
-            self.dataset = ArtificialTestDataset(self.data_dir / "Test")
+            self.dataset = ArtificialTestDataset(self.data_dir / "Test", self.png_decoder)
         elif synthetic == "artificial":
             self.dataset = SyntheticArtificialTest(n_frames, height, width)
         elif synthetic == "video_u8":
@@ -446,7 +578,7 @@ class DataModule:
         """[artificial, real-world] like utils/data.py:168-179 (the second only when its directory exists)"""
         loaders = [self.dataset]
         if self.data_dir is not None and (self.data_dir / "Real-World Test").is_dir():
-            loaders.append(RealWorldTestDataset(self.data_dir / "Real-World Test"))
+            loaders.append(RealWorldTestDataset(self.data_dir / "Real-World Test", self.png_decoder))
         return loaders
 
     def val_dataloader(self):
@@ -456,14 +588,14 @@ class DataModule:
             raise ValueError("val_dataloader needs data.crop_size (and takes data.image_repeats, data.batch_size)")
         repeats = 1 if self.image_repeats is None else self.image_repeats
         if self.data_dir is not None and (self.data_dir / "Validation").is_dir():
-            artificial = ArtificialTrainValDataset(self.data_dir / "Validation", self.crop_size, repeats)
+            artificial = ArtificialTrainValDataset(self.data_dir / "Validation", self.crop_size, repeats, self.png_decoder)
         elif synthetic == "trainval":
             artificial = SyntheticTrainVal(n_frames, height, width, self.crop_size, repeats)
         else:
             raise ValueError("no %s directory: `data.synthetic: trainval` makes a synthetic validation set"
                              % (self.data_dir / "Validation" if self.data_dir is not None else "data_dir / Validation"))
         if self.data_dir is not None and (self.data_dir / "Real-World Test").is_dir():
-            real = RealWorldTestDataset(self.data_dir / "Real-World Test")
+            real = RealWorldTestDataset(self.data_dir / "Real-World Test", self.png_decoder)
         else:
             real = SyntheticStereoFrames(n_frames, height, width)
-        return [BatchLoader(artificial, self.batch_size, "artificial"), BatchLoader(real, 1, "real-world")]
+        return [BatchLoader(artificial, self.batch_size, "artificial", self.decode_ahead), BatchLoader(real, 1, "real-world", self.decode_ahead)]

@@ -4,9 +4,11 @@ A PNG file is a signature and a list of chunks `length, type, data, CRC-32(type 
 data is ONE zlib stream (RFC 1950: two header bytes, deflate blocks, the Adler-32 of the uncompressed bytes) of the filtered rows.
 The device delivers that stream in pieces that each end on a byte boundary and contain no final block, with the Adler-32 of each
 piece's own bytes; what is left for the host is arithmetic on a few numbers and one `zlib.crc32` over the compressed bytes (which
-releases the GIL, so the writer's threads run it in parallel).  Pure Python, `zlib` and `struct` only."""
+releases the GIL, so the writer's threads run it in parallel).  `parse` is the same container read: the chunks checked, the IDAT
+payload handed on as it is for ct_hip.png_decode to inflate and unfilter on the device.  Pure Python, `zlib` and `struct` only."""
 import struct
 import zlib
+from collections import namedtuple
 
 ADLER_MOD = 65521
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
@@ -54,3 +56,51 @@ def chunk_rows(height, rows_per_chunk):
     """the number of rows of each chunk of a frame: rows_per_chunk (at most the height), the last one what is left"""
     rows = min(int(rows_per_chunk), int(height))
     return [min(rows, height - r) for r in range(0, height, rows)]
+
+
+PngInfo = namedtuple("PngInfo", "height width bit_depth colour_type interlace payload")
+
+
+def parse(data):
+    """The container of a PNG file: PngInfo(height, width, bit_depth, colour_type, interlace, payload), payload = the data of
+    every IDAT chunk concatenated = ONE zlib stream of the filtered rows (not inflated here).  Checked: the signature, every chunk's
+    CRC-32, IHDR first, IEND present; a ValueError names what is wrong.  Ancillary chunks are skipped (their CRC is still checked)."""
+    data = bytes(data)
+    if data[:8] != SIGNATURE:
+        raise ValueError("not a PNG file: bad signature %r" % data[:8])
+    at, first, ihdr, idat, ended = 8, True, None, [], False
+    while at < len(data):
+        if at + 8 > len(data):
+            raise ValueError("truncated PNG file: a chunk header at byte %d of %d" % (at, len(data)))
+        length, kind = struct.unpack(">I4s", data[at:at + 8])
+        end = at + 12 + length
+        if end > len(data):
+            raise ValueError("truncated PNG file: chunk %r at byte %d needs %d bytes, %d are left" % (kind, at, 12 + length, len(data) - at))
+        body = data[at + 8:at + 8 + length]
+        crc, = struct.unpack(">I", data[end - 4:end])
+        if zlib.crc32(body, zlib.crc32(kind)) != crc:
+            raise ValueError("chunk %r at byte %d: CRC-32 mismatch" % (kind, at))
+        if first and kind != b"IHDR":
+            raise ValueError("the first chunk is %r, not IHDR" % kind)
+        first = False
+        if kind == b"IHDR":
+            if ihdr is not None or length != 13:
+                raise ValueError("a second IHDR chunk" if ihdr is not None else "IHDR of %d bytes, not 13" % length)
+            ihdr = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            ended = True
+            break
+        at = end
+    if ihdr is None:
+        raise ValueError("truncated PNG file: no IHDR chunk")
+    if not ended:
+        raise ValueError("truncated PNG file: no IEND chunk")
+    width, height, depth, colour, _, _, interlace = ihdr
+    return PngInfo(height, width, depth, colour, interlace, b"".join(idat))
+
+
+def device_decodable(info):
+    """what ct_hip.png_decode takes: 8 bits per sample, colour type 2 (RGB), not interlaced"""
+    return info.bit_depth == 8 and info.colour_type == 2 and info.interlace == 0 and info.height >= 1 and info.width >= 1

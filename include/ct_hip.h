@@ -652,6 +652,42 @@ long long ct_png_slot_capacity(int h, int w, int rows_per_chunk);
 int ct_png_deflate_u8(const uint8_t *frames, int n, int h, int w, int rows_per_chunk, uint8_t *streams, long long capacity,
                       int *sizes, unsigned int *adler, void *stream);
 
+/* ---- PNG decoding: the other direction, csrc/png_decode.hip (+ csrc/ct_inflate.h, the serial core, which also compiles on the
+ * host).  For the files the reference's datasets hold: 8 bits, colour type 2, no interlace; the container is host work
+ * (utils/png.py: parse).  Entries added under ABI 9 (no argument list changed).
+ *
+ * Per-stream status, written by both kernels: */
+#define CT_INFLATE_OK 0
+#define CT_INFLATE_BAD_HEADER 1        /* zlib header: CM != 8, CINFO > 7, FDICT set or not divisible by 31 */
+#define CT_INFLATE_BLOCK_TYPE 2        /* the reserved block type 3 */
+#define CT_INFLATE_STORED_LEN 3        /* stored block: LEN != ~NLEN */
+#define CT_INFLATE_OVERSUBSCRIBED 4    /* code lengths over-subscribed */
+#define CT_INFLATE_INCOMPLETE 5        /* code lengths incomplete (one distance or literal code of one bit is allowed), no end-of-block code */
+#define CT_INFLATE_REPEAT 6            /* repeat symbol with no previous length, or running past HLIT + HDIST */
+#define CT_INFLATE_INVALID_SYMBOL 7    /* 286 / 287, distance 30 / 31, bits that are no code, HLIT > 286, HDIST > 30 */
+#define CT_INFLATE_DISTANCE 8          /* distance beyond the start of the output */
+#define CT_INFLATE_INPUT_EXHAUSTED 9
+#define CT_INFLATE_OUTPUT_TOO_LARGE 10 /* the stream holds more than its slot (or the slot is above 2^31 - 1 bytes) */
+#define CT_INFLATE_OUTPUT_TOO_SMALL 11 /* the stream ended before the slot was full */
+#define CT_INFLATE_ADLER 12            /* Adler-32 mismatch */
+#define CT_INFLATE_FILTER 13           /* ct_png_unfilter_u8: a filter-type byte above 4 */
+#define CT_INFLATE_DIMS 14             /* ct_png_unfilter_u8: h or w < 1, w > CT_PNG_MAX_WIDTH, or sizes that are not h (1 + 3 w) / 3 h w */
+#define CT_PNG_MAX_WIDTH 8192          /* a row of packed pixels is handed from band to band in LDS */
+/* ct_png_inflate_u8: n zlib streams (RFC 1950) back to back in src, stream i = bytes [src_offsets[i], src_offsets[i + 1]) at any
+ *   alignment, inflated into dst bytes [dst_offsets[i], dst_offsets[i + 1]): it must inflate to exactly that many (< 2^31).
+ *   src_offsets, dst_offsets: int64 [n + 1] ON THE DEVICE.  status [n] int32 and adler_out [n] uint32 (the Adler-32 of what was
+ *   written, compared on the device with the stream's trailer) are written for every stream.  Nothing outside a stream's bytes is
+ *   read and nothing outside its slot written, whatever the bytes are; a slot of a stream that fails holds an unspecified prefix.
+ *   One 64-lane workgroup per stream, 37.5 KB of LDS (the 32 KB window as a ring), no workspace, asynchronous, deterministic.
+ * ct_png_unfilter_u8: stream i = h (1 + 3 w) filtered bytes at filtered + offsets[i] (dims [n][2] int32 = h, w; offsets and
+ *   dst_offsets int64 [n + 1], all on the device) -> planar uint8 [3][h][w] at dst + dst_offsets[i].  All five filter types of
+ *   the PNG specification.  A stream whose status is not 0 on entry is skipped; status is set to CT_INFLATE_FILTER / _DIMS.
+ * Both: CT_E_BADARG: a null pointer or n < 1; CT_E_ALIGN: an int64 array off 8 bytes, status / adler_out / dims off 4.        */
+int ct_png_inflate_u8(const uint8_t *src, const long long *src_offsets, int n, uint8_t *dst, const long long *dst_offsets, int *status,
+                      unsigned int *adler_out, void *stream);
+int ct_png_unfilter_u8(const uint8_t *filtered, const long long *offsets, const int *dims, int n, uint8_t *dst,
+                       const long long *dst_offsets, int *status, void *stream);
+
 /* ---- training / validation samples (utils/data.py:25-84: ArtificialTrainValDataset.__getitem__ + apply_uniform_distortions),
  * csrc/augment.hip.  Entries added under ABI 9 (no argument list changed).  One call makes a batch of n samples from n source
  * pairs gt, ref: uint8 [n][3][height][width].  Per sample (ct_augment_sample):
