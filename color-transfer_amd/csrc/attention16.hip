@@ -24,61 +24,11 @@
 #include <cmath>
 #include "ct_attention16.h"
 #include "ct_env.h"
+#include "ct_split16.h"    // the fp16 two-piece primitives and ct_wave.h: device inline code only, no kernel
 
 namespace ct {
 
-typedef float f32x16h __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2h __attribute__((ext_vector_type(2)));
-
 static constexpr float kLog2eH = 1.4426950408889634f, kLn2H = 0.6931471805599453f;
-
-// max over the wave of a non-negative float; every lane returns it
-__device__ __forceinline__ float wave_max_nonneg_h(float v) {
-    int x = __float_as_int(v);      // non-negative floats order like their bit patterns
-#define CT_DPP_MAX(ctrl, rmask) x = max(x, __builtin_amdgcn_update_dpp(0, x, ctrl, rmask, 0xf, false))
-    CT_DPP_MAX(0x111, 0xf);         // row_shr:1
-    CT_DPP_MAX(0x112, 0xf);         // row_shr:2
-    CT_DPP_MAX(0x114, 0xf);         // row_shr:4
-    CT_DPP_MAX(0x118, 0xf);         // row_shr:8   -> lane 15 of every row holds the row maximum
-    CT_DPP_MAX(0x142, 0xa);         // row_bcast:15 into rows 1 and 3
-    CT_DPP_MAX(0x143, 0xc);         // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave maximum
-#undef CT_DPP_MAX
-    return __int_as_float(__builtin_amdgcn_readlane(x, 63));
-}
-
-// opaque to the compiler (it otherwise re-derives each half with v_fma_mixlo_f16 when the halves are converted back)
-__device__ __forceinline__ unsigned int cvt_pk_f16h(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void split2x2h(float x0, float x1, unsigned int &hw, unsigned int &lw) {
-    hw = cvt_pk_f16h(x0, x1);
-    const f16x2h h = __builtin_bit_cast(f16x2h, hw);
-    lw = cvt_pk_f16h(x0 - (float)h.x, x1 - (float)h.y);
-}
-__device__ __forceinline__ void split2x8h(const float (&x)[8], uint4 &h, uint4 &l) {
-    unsigned int hw[4], lw[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split2x2h(x[2 * i], x[2 * i + 1], hw[i], lw[i]);
-    h = make_uint4(hw[0], hw[1], hw[2], hw[3]); l = make_uint4(lw[0], lw[1], lw[2], lw[3]);
-}
-// s += A . B with A, B given as (hi, lo) fragments; small terms first
-__device__ __forceinline__ void mfma_split3h(f32x16h &s, const uint4 (&a)[2], const uint4 (&b)[2]) {
-    const f16x8h ah = __builtin_bit_cast(f16x8h, a[0]), al = __builtin_bit_cast(f16x8h, a[1]);
-    const f16x8h bh = __builtin_bit_cast(f16x8h, b[0]), bl = __builtin_bit_cast(f16x8h, b[1]);
-    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, s, 0, 0, 0);
-    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, s, 0, 0, 0);
-    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, s, 0, 0, 0);
-}
-// exponent e with 2^e * mx in [2^11, 2^12); `none` for mx == 0 / denormal (no constraint); 0 for inf / NaN (they propagate)
-__device__ __forceinline__ int scale_exp_h(float mx, int none) {
-    const int fld = (int)(__float_as_uint(mx) >> 23);                  // biased exponent (mx >= 0)
-    const int ex = fld == 0 ? none : fld == 255 ? 0 : 138 - fld;       // 12 - (floor(log2 mx) + 1)
-    return min(max(ex, -100), 100);
-}
-__device__ __forceinline__ float pow2i_h(int e) { return __uint_as_float((unsigned int)(127 + e) << 23); }   // |e| <= 126
 
 constexpr int kSsRowH(int C) { return 2 * C + 16; }   // bytes per LDS row of a tile image: 16-byte fragment reads are conflict free
 
@@ -160,13 +110,13 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
             for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(x[st][j]));
         }
         amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const int eq = scale_exp_h(amax, 0);
-        sq = pow2i_h(eq); gq = pow2i_h(-eq);
+        const int eq = sp16_scale_exp(amax, 0);
+        sq = sp16_pow2i(eq); gq = sp16_pow2i(-eq);
 #pragma unroll
         for (int st = 0; st < C / 16; ++st) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[st][j] *= sq;
-            split2x8h(x[st], qf[st][0], qf[st][1]);
+            sp16_split2x8(x[st], qf[st][0], qf[st][1]);
         }
     }
     const int qreg = region ? region[tb + qclamp] : 0;
@@ -224,36 +174,36 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
 #pragma unroll
             for (int i = 0; i < VV4; ++i) mv = fmaxf(mv, amax4(vpre[i]));
         }
-        mk = wave_max_nonneg_h(mk);
-        if constexpr (PVS) mv = wave_max_nonneg_h(mv);
+        mk = wave_max_nonneg(mk);
+        if constexpr (PVS) mv = wave_max_nonneg(mv);
         if (lane == 0) { Mx[2 * wave] = mk; Mx[2 * wave + 1] = mv; }
     };
     int e_stage = 100, e_cur = 100;                 // running V exponent: of the staged tile / of the accumulators' domain
     auto stage = [&]() {
         const float4 m0 = *reinterpret_cast<const float4 *>(Mx), m1 = *reinterpret_cast<const float4 *>(Mx + 4);
-        const int ek = __builtin_amdgcn_readfirstlane(scale_exp_h(fmaxf(fmaxf(m0.x, m0.z), fmaxf(m1.x, m1.z)), 0));
-        const float sk = pow2i_h(ek);
-        if (tid == 0) { Gs[0] = pow2i_h(-ek); Gs[1] = sk; }
+        const int ek = __builtin_amdgcn_readfirstlane(sp16_scale_exp(fmaxf(fmaxf(m0.x, m0.z), fmaxf(m1.x, m1.z)), 0));
+        const float sk = sp16_pow2i(ek);
+        if (tid == 0) { Gs[0] = sp16_pow2i(-ek); Gs[1] = sk; }
 #pragma unroll
         for (int i = 0; i < KV4; ++i) {
             const int f = tid + i * 256, key = f / (C / 4), c4 = f - key * (C / 4);
             unsigned int h0, l0, h1, l1;
-            split2x2h(kpre[i].x * sk, kpre[i].y * sk, h0, l0);
-            split2x2h(kpre[i].z * sk, kpre[i].w * sk, h1, l1);
+            sp16_split2x2(kpre[i].x * sk, kpre[i].y * sk, h0, l0);
+            sp16_split2x2(kpre[i].z * sk, kpre[i].w * sk, h1, l1);
             unsigned char *kd = Ks + key * SROW + 8 * c4;
             *reinterpret_cast<uint2 *>(kd) = make_uint2(h0, h1);
             *reinterpret_cast<uint2 *>(kd + 32 * SROW) = make_uint2(l0, l1);
         }
         if constexpr (PVS) {
-            const int ev = scale_exp_h(fmaxf(fmaxf(m0.y, m0.w), fmaxf(m1.y, m1.w)), 100);
+            const int ev = sp16_scale_exp(fmaxf(fmaxf(m0.y, m0.w), fmaxf(m1.y, m1.w)), 100);
             e_stage = __builtin_amdgcn_readfirstlane(min(e_stage, ev));
-            const float sv = pow2i_h(e_stage);
+            const float sv = sp16_pow2i(e_stage);
 #pragma unroll
             for (int i = 0; i < VV4; ++i) {
                 const int f = tid + i * 256, key = f / (CV / 4), c4 = f - key * (CV / 4);
                 unsigned int h0, l0, h1, l1;
-                split2x2h(vpre[i].x * sv, vpre[i].y * sv, h0, l0);
-                split2x2h(vpre[i].z * sv, vpre[i].w * sv, h1, l1);
+                sp16_split2x2(vpre[i].x * sv, vpre[i].y * sv, h0, l0);
+                sp16_split2x2(vpre[i].z * sv, vpre[i].w * sv, h1, l1);
                 unsigned char *vd = Vs + key * VROWB + 8 * c4;
                 *reinterpret_cast<uint2 *>(vd) = make_uint2(h0, h1);
                 *reinterpret_cast<uint2 *>(vd + 32 * VROWB) = make_uint2(l0, l1);
@@ -265,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
     };
 
     float m_run = -INFINITY, l_run = 0.f, a_run = 0.f;     // a_run: sum_j p_j (j - i) in the domain of l_run (IDX)
-    f32x16h o[NVT];
+    f32x16 o[NVT];
     float o2x = 0.f, o2y = 0.f;
     if constexpr (PVS) {
 #pragma unroll
@@ -292,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
             fetch_rows(j0 + 64);
         }
         // ---- S^T tile: A = K rows (key nl) from LDS, B = Q; LDS operand reads run one group ahead of the MFMAs ----
-        f32x16h s;
+        f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
         {
@@ -306,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
 #pragma unroll
                     for (int p = 0; p < 2; ++p) an[p] = *reinterpret_cast<const uint4 *>(kp + p * 32 * SROW + 32 * (st + 1));
                 }
-                mfma_split3h(s, ac, qf[st]);
+                sp16_mfma3(s, ac, qf[st]);
 #pragma unroll
                 for (int p = 0; p < 2; ++p) ac[p] = an[p];
             }
@@ -369,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
             for (int t = 0; t < 2; ++t) {
                 const float x[8] = {s[8 * t], s[8 * t + 1], s[8 * t + 2], s[8 * t + 3], s[8 * t + 4], s[8 * t + 5], s[8 * t + 6], s[8 * t + 7]};
                 uint4 pf[2];
-                split2x8h(x, pf[0], pf[1]);
+                sp16_split2x8(x, pf[0], pf[1]);
 #pragma unroll
                 for (int j = 0; j < NVT; ++j) {
                     uint4 vf[2];
@@ -381,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void attention16_tokens_kernel(const float 
                         const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
                         vf[p] = make_uint4(l2.x, l2.y, h2.x, h2.y);
                     }
-                    mfma_split3h(o[j], vf, pf);
+                    sp16_mfma3(o[j], vf, pf);
                 }
             }
         } else if constexpr (CV == 2) {
@@ -481,14 +431,14 @@ __global__ __launch_bounds__(256, 2) void attention16_colsum_kernel(const float 
             for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(x[st][j]));
         }
         amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const int ek = scale_exp_h(amax, 0);
-        const float sk = pow2i_h(ek);
-        gk = pow2i_h(-ek);
+        const int ek = sp16_scale_exp(amax, 0);
+        const float sk = sp16_pow2i(ek);
+        gk = sp16_pow2i(-ek);
 #pragma unroll
         for (int st = 0; st < C / 16; ++st) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[st][j] *= sk;
-            split2x8h(x[st], kf[st][0], kf[st][1]);
+            sp16_split2x8(x[st], kf[st][0], kf[st][1]);
         }
     }
     float4 qpre[QV4];
@@ -509,20 +459,20 @@ __global__ __launch_bounds__(256, 2) void attention16_colsum_kernel(const float 
 #pragma unroll
         for (int i = 0; i < QV4; ++i)
             m = fmaxf(m, fmaxf(fmaxf(fabsf(qpre[i].x), fabsf(qpre[i].y)), fmaxf(fabsf(qpre[i].z), fabsf(qpre[i].w))));
-        m = wave_max_nonneg_h(m);
+        m = wave_max_nonneg(m);
         if (lane == 0) Mx[wave] = m;
     };
     auto stage = [&]() {
         const float4 m0 = *reinterpret_cast<const float4 *>(Mx);
-        const int eq = __builtin_amdgcn_readfirstlane(scale_exp_h(fmaxf(fmaxf(m0.x, m0.y), fmaxf(m0.z, m0.w)), 0));
-        const float sqv = pow2i_h(eq);
-        if (tid == 0) Gs[0] = pow2i_h(-eq);
+        const int eq = __builtin_amdgcn_readfirstlane(sp16_scale_exp(fmaxf(fmaxf(m0.x, m0.y), fmaxf(m0.z, m0.w)), 0));
+        const float sqv = sp16_pow2i(eq);
+        if (tid == 0) Gs[0] = sp16_pow2i(-eq);
 #pragma unroll
         for (int i = 0; i < QV4; ++i) {
             const int f = tid + i * 256, qq = f / (C / 4), c4 = f - qq * (C / 4);
             unsigned int h0, l0, h1, l1;
-            split2x2h(qpre[i].x * sqv, qpre[i].y * sqv, h0, l0);
-            split2x2h(qpre[i].z * sqv, qpre[i].w * sqv, h1, l1);
+            sp16_split2x2(qpre[i].x * sqv, qpre[i].y * sqv, h0, l0);
+            sp16_split2x2(qpre[i].z * sqv, qpre[i].w * sqv, h1, l1);
             unsigned char *qd = Qs + qq * SROW + 8 * c4;
             *reinterpret_cast<uint2 *>(qd) = make_uint2(h0, h1);
             *reinterpret_cast<uint2 *>(qd + 32 * SROW) = make_uint2(l0, l1);
@@ -538,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void attention16_colsum_kernel(const float 
     for (int i0 = 0; i0 < L; i0 += 32) {
         const bool more = i0 + 32 < L;
         if (more) fetch(i0 + 32);
-        f32x16h s;
+        f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
         const unsigned char *qp = Qs + nl * SROW + 16 * hl;
@@ -551,7 +501,7 @@ __global__ __launch_bounds__(256, 2) void attention16_colsum_kernel(const float 
 #pragma unroll
                 for (int p = 0; p < 2; ++p) an[p] = *reinterpret_cast<const uint4 *>(qp + p * 32 * SROW + 32 * (st + 1));
             }
-            mfma_split3h(s, ac, kf[st]);
+            sp16_mfma3(s, ac, kf[st]);
 #pragma unroll
             for (int p = 0; p < 2; ++p) ac[p] = an[p];
         }

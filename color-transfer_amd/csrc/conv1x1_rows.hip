@@ -12,11 +12,11 @@
 // products, float32 accumulation in the matrix pipe's order -- the "exact" class of cnn.hip, closer to the reference than the two-piece
 // form it replaces.
 #include "ct_common.h"
+#include "ct_split16.h"      // f32x16
 #include <type_traits>
 
 namespace ct {
 
-typedef float f32x16r __attribute__((ext_vector_type(16)));
 typedef float f32x4r __attribute__((ext_vector_type(4)));
 
 struct Rows1x1Args {
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rows_kernel(Rows1x1Args a) {
 #pragma unroll
             for (int st = 0; st < 32; ++st) xb[CUR ^ 1][st] = p[(size_t)(2 * st) * plane];
         }
-        f32x16r acc[NMB];
+        f32x16 acc[NMB];
 #pragma unroll
         for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll

@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
 #pragma unroll
             for (int j = 0; j < PFE; ++j) mx = fmaxf(mx, fabsf(pfe[j]));
         }
-        mx = sp16_wave_max(mx);
+        mx = wave_max_nonneg(mx);
         if (lane == 0) mxw[wave] = mx;
     };
     auto tile_exp = [&]() {
@@ -458,10 +458,10 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
             if constexpr (F16) {
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-                    const f16x8s ah = __builtin_bit_cast(f16x8s, w[0][m]), al = __builtin_bit_cast(f16x8s, w[1][m]);
+                    const f16x8 ah = __builtin_bit_cast(f16x8, w[0][m]), al = __builtin_bit_cast(f16x8, w[1][m]);
 #pragma unroll
                     for (int q = 0; q < RPW; ++q) {        // small terms first
-                        const f16x8s bh = __builtin_bit_cast(f16x8s, b[q][0]), bl = __builtin_bit_cast(f16x8s, b[q][1]);
+                        const f16x8 bh = __builtin_bit_cast(f16x8, b[q][0]), bl = __builtin_bit_cast(f16x8, b[q][1]);
                         acc[q][m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[q][m], 0, 0, 0);
                         acc[q][m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[q][m], 0, 0, 0);
                         acc[q][m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[q][m], 0, 0, 0);

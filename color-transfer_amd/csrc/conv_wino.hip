@@ -38,23 +38,7 @@ constexpr size_t kWnVBytes = (size_t)16 * 2 * 2 * 64 * 16;                      
 constexpr size_t kWnMBytes = (size_t)16 * 1024 * sizeof(float);                  // [position][cout block][i][k][tile]: the position's V bytes
 constexpr size_t kWnLds = kWnRingBytes + (kWnMBytes > kWnVBytes ? kWnMBytes : kWnVBytes) + 64;
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4w __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned int wn_cvt_pk(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float wn_wave_max(float v) {        // v >= 0; every lane returns the maximum
-    int x = __float_as_int(v);
-#define CT_DPP_MAX(ctrl, rmask) x = max(x, __builtin_amdgcn_update_dpp(0, x, ctrl, rmask, 0xf, false))
-    CT_DPP_MAX(0x111, 0xf); CT_DPP_MAX(0x112, 0xf); CT_DPP_MAX(0x114, 0xf); CT_DPP_MAX(0x118, 0xf);
-    CT_DPP_MAX(0x142, 0xa); CT_DPP_MAX(0x143, 0xc);
-#undef CT_DPP_MAX
-    return __int_as_float(__builtin_amdgcn_readlane(x, 63));
-}
 
 // ACTK: compile-time activation (0 none, 1 LeakyReLU(0.01), 2 ReLU, 3 = switch over a.act at run time), as in conv_ws.hip
 // HAS_RES: a skip tensor is added after the activation; without one no skip row is requested at all (round 6: the no-skip launches
@@ -170,7 +154,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                 float m = 0.f;
                 stage(2 * pr, 2 * pr, p0[2 * pr], p1[2 * pr], m);
                 stage(2 * pr + 1, 2 * pr + 1, p0[2 * pr + 1], p1[2 * pr + 1], m);
-                m = wn_wave_max(m);
+                m = wave_max_nonneg(m);
                 if (lane == 0) atomicMax(rowmax + pr, __float_as_uint(m));
             }
         }
@@ -284,8 +268,8 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                     for (int q = 0; q < 2; ++q)
 #pragma unroll
                         for (int mb = 0; mb < 4; ++mb)
-                            acc[q][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, wreg[q][mb][kc][pw]),
-                                                                                __builtin_bit_cast(h16x8, bq[q][pv]), acc[q][mb], 0, 0, 0);
+                            acc[q][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wreg[q][mb][kc][pw]),
+                                                                                __builtin_bit_cast(f16x8, bq[q][pv]), acc[q][mb], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 };
                 float m = 0.f;
@@ -301,7 +285,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                 stage(2 * s + 5, (SB + 5) % kWnRing, nb0, nb1, m);
                 __builtin_amdgcn_sched_barrier(0);
                 group(0, 2, bq0);
-                m = wn_wave_max(m);
+                m = wave_max_nonneg(m);
                 if (lane == 0) atomicMax(rowmax + ((SB + 4) % kWnRing) / 2, __float_as_uint(m));
                 __builtin_amdgcn_sched_barrier(0);
                 group(1, 0, bq1);

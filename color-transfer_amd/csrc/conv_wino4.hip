@@ -299,12 +299,8 @@ __device__ __forceinline__ void do_op(St &st, const Ctx &cx, const LoadF &load_r
         else asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(st.mx4[idx & 3]) : "v"(q[2 * half]), "v"(q[2 * half + 1]));
     } else if constexpr (o.kind == OP_MXF) {
         float m = fmaxf(fmaxf(st.mx4[0], st.mx4[1]), fmaxf(st.mx4[2], st.mx4[3]));
-        int x = __float_as_int(m);
-#define CT_DPP_MAX(ctrl, rmask) x = max(x, __builtin_amdgcn_update_dpp(0, x, ctrl, rmask, 0xf, false))
-        CT_DPP_MAX(0x111, 0xf); CT_DPP_MAX(0x112, 0xf); CT_DPP_MAX(0x114, 0xf); CT_DPP_MAX(0x118, 0xf);
-        CT_DPP_MAX(0x142, 0xa); CT_DPP_MAX(0x143, 0xc);
-#undef CT_DPP_MAX
-        if (cx.lane63) *cx.rowmax_w = __int_as_float(x);
+        m = wave_max_nonneg_lane63(m);
+        if (cx.lane63) *cx.rowmax_w = m;
     } else {                                    // OP_ST: four columns of one output row of one cout
         constexpr int k = o.r, a = o.a;
 #ifdef W4_ABL_NO_ST
@@ -510,12 +506,8 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
                         asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(q[0]), "v"(q[1]));
                         asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(q[2]), "v"(q[3]));
                     }
-            int x = __float_as_int(m);
-#define CT_DPP_MAX(ctrl, rmask) x = max(x, __builtin_amdgcn_update_dpp(0, x, ctrl, rmask, 0xf, false))
-            CT_DPP_MAX(0x111, 0xf); CT_DPP_MAX(0x112, 0xf); CT_DPP_MAX(0x114, 0xf); CT_DPP_MAX(0x118, 0xf);
-            CT_DPP_MAX(0x142, 0xa); CT_DPP_MAX(0x143, 0xc);
-#undef CT_DPP_MAX
-            if (lane == 63) rowmax[(k & 3) * 4 + wave] = __int_as_float(x);
+            m = wave_max_nonneg_lane63(m);
+            if (lane == 63) rowmax[(k & 3) * 4 + wave] = m;
         };
         // the scale of step t (pairs t, t + 1): 2^ex max |x| in [2^9, 2^10), so |V| <= 4 max |x| stays below 2^12 (conv_wino.hip).
         // In two halves: the LDS reads at the head of a step, the arithmetic a few slices later (nothing waits for the reads)

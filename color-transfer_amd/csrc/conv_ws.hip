@@ -34,30 +34,8 @@ constexpr int kWsPS = 36;                    // floats per row of a partial-sum 
 constexpr int kWsChunks = 4;                 // 16-channel chunks = SIMDs
 constexpr int kWsWaves = 8;                  // (chunk, 32-channel half of the outputs)
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// max over the wave of a non-negative float (DPP row shifts + row broadcasts; every lane returns the maximum)
-__device__ __forceinline__ float wave_max_nonneg(float v) {
-    int x = __float_as_int(v);      // non-negative floats order like their bit patterns
-#define CT_DPP_MAX(ctrl, rmask) x = max(x, __builtin_amdgcn_update_dpp(0, x, ctrl, rmask, 0xf, false))
-    CT_DPP_MAX(0x111, 0xf);         // row_shr:1
-    CT_DPP_MAX(0x112, 0xf);         // row_shr:2
-    CT_DPP_MAX(0x114, 0xf);         // row_shr:4
-    CT_DPP_MAX(0x118, 0xf);         // row_shr:8   -> lane 15 of every row holds the row maximum
-    CT_DPP_MAX(0x142, 0xa);         // row_bcast:15 into rows 1 and 3
-    CT_DPP_MAX(0x143, 0xc);         // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave maximum
-#undef CT_DPP_MAX
-    return __int_as_float(__builtin_amdgcn_readlane(x, 63));
-}
-
-// two float32 -> packed fp16 (round to nearest even), opaque to the compiler (it otherwise recomputes each half with
-// v_fma_mixlo_f16 when the halves are converted back for the residual)
-__device__ __forceinline__ f16x2 cvt_pk_f16(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return __builtin_bit_cast(f16x2, r);
-}
+// sp16_cvt_pk as a vector of two halves
+__device__ __forceinline__ f16x2 cvt_pk_f16(float a, float b) { return __builtin_bit_cast(f16x2, sp16_cvt_pk(a, b)); }
 
 // F16: the operands are split into TWO fp16 pieces (11 + 11 mantissa bits) and a product is three MFMAs
 // (a_hi b_hi + a_hi b_lo + a_lo b_hi; what is dropped is 2^-22 relative) instead of six bf16 ones: half the matrix work, which

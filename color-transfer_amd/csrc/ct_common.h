@@ -7,6 +7,7 @@
 
 #include "../../include/ct_hip.h"
 #include "ct_env.h"      // ct::env_int / ct::env_str: the start-up switches
+#include "ct_wave.h"     // the wave reductions
 
 namespace ct {
 
@@ -176,15 +177,11 @@ __device__ __forceinline__ void store12<double>(double *p, bool vec, const doubl
 }
 
 // ---- deterministic block sum of NV doubles per thread ------------------------------------
-// wave: __shfl_down tree (fixed shape); block: 4 wave leaders through LDS, added in wave
-// order by thread 0.  Result valid in thread 0 only.
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double *lds /* [4][NV] */) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] += __shfl_down(v[i], off, kWave);
-    }
+// wave: ct_wave.h's __shfl_down tree (fixed shape); block: the NW wave leaders through LDS,
+// added in wave order by thread 0.  Result valid in thread 0 only.
+template <int NV, int NW = 4>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double *lds /* [NW][NV] */) {
+    wave_sum(v);
     const int lane = threadIdx.x & (kWave - 1);
     const int wid = threadIdx.x >> 6;
     if (lane == 0) {
@@ -194,7 +191,11 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *lds /* [4][NV
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] = ((lds[i] + lds[NV + i]) + lds[2 * NV + i]) + lds[3 * NV + i];
+        for (int i = 0; i < NV; ++i) {
+            double a = lds[i];
+            for (int w = 1; w < NW; ++w) a += lds[w * NV + i];   // wave order: fixed
+            v[i] = a;
+        }
     }
 }
 

@@ -1,7 +1,8 @@
-// ct_png.h -- the serial part of csrc/png.hip: Huffman code lengths of at most 15 bits from sorted symbol counts.  Plain C++ on
-// plain arrays (the kernel hands it LDS, a host program hands it memory), so that it can be compiled and checked on the CPU.
+// ct_png.h -- what csrc/png.hip and csrc/png_decode.hip share, and the serial part of the encoder: the Paeth predictor, and Huffman
+// code lengths of at most 15 bits from sorted symbol counts.  Plain C++ on plain arrays (the kernel hands it LDS, a host program hands it memory), so that it can be compiled and checked on the CPU.
 #pragma once
 #include <stdint.h>
+#include <stdlib.h>
 
 #if defined(__HIPCC__)
 #define CT_PNG_HD __host__ __device__ __forceinline__
@@ -12,6 +13,13 @@
 namespace ct {
 
 constexpr int kPngMaxBits = 15;                             // RFC 1951: no literal / length code is longer
+
+// PNG filter type 4 (a: left, b: above, c: above left), of the encoder's filter choice and the decoder's unfilter
+CT_PNG_HD unsigned int paeth(unsigned int a, unsigned int b, unsigned int c) {
+    const int p = (int)a + (int)b - (int)c;
+    const int pa = abs(p - (int)a), pb = abs(p - (int)b), pc = abs(p - (int)c);
+    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);         // ties: a, then b, then c
+}
 
 // a[0 .. n): the counts of the n >= 2 used symbols in ascending order.  On return a[i] is the code length of the i-th of them
 // (the rarest symbol first: lengths descend), count[l] the number of codes of l bits (l = 0 .. 15, count[0] = 0) and

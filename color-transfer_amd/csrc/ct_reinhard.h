@@ -158,28 +158,4 @@ __device__ __forceinline__ double uniform_f64(double v) {     // wave-uniform do
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-template <int NV, int NW>
-__device__ __forceinline__ void block_sum_n(double (&v)[NV], double *lds /* [NW][NV] */) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] += __shfl_down(v[i], off, kWave);
-    }
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wid = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) lds[wid * NV + i] = v[i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            double a = lds[i];
-            for (int w = 1; w < NW; ++w) a += lds[w * NV + i];   // wave order: fixed
-            v[i] = a;
-        }
-    }
-}
-
 }  // namespace ct

@@ -114,8 +114,7 @@ __global__ __launch_bounds__(256) void regress_index_kernel(const float *__restr
     }
     const int tail0 = head + 4 * nb4;
     if (tail0 + lane < w) acc = fmaf(a[tail0 + lane], (float)(tail0 + lane), acc);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_all_sum(acc);
     if (lane == 0) disp[qrow] = (float)(int)(qrow % w) - acc;
 }
 

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kLutBlock, kLutMinWaves) void lab_moments_lut_kerne
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) s[i] += (double)sf[i];
-    block_sum_n<6, kLutWaves>(s, red);
+    block_sum<6, kLutWaves>(s, red);
     if (threadIdx.x == 0) {
         double *dst = partials + ((size_t)img * kMaxBlocksPerImage + blockIdx.x) * kPartialStride;
 #pragma unroll
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(kLutBlock, kLutMinWaves) void reinhard_apply_lut_ke
     if (gt != nullptr) {                                             // uniform per launch
         double v[1] = {sq};
         __syncthreads();                                             // fin[] is free again
-        block_sum_n<1, kLutWaves>(v, fin);
+        block_sum<1, kLutWaves>(v, fin);
         if (threadIdx.x == 0) sq_partials[(size_t)img * kMaxBlocksPerImage + blockIdx.x] = v[0];
     }
 }

@@ -155,8 +155,7 @@ __global__ __launch_bounds__(256) void layernorm_tokens_kernel(const float *__re
         v.x += u.x; v.y += u.y;
     }
     float s = v.x + v.y;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_all_sum(s);
     const float mean = s * (1.0f / 128.0f);
     const float dx = v.x - mean, dy = v.y - mean;
     float ss = dx * dx + dy * dy;

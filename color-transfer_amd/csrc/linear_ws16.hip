@@ -25,29 +25,9 @@
 
 namespace ct {
 
-typedef _Float16 f16x8w __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2w __attribute__((ext_vector_type(2)));
-
 // uint4 entries of one slice image: [piece][k step][lane half][feature] x 8 channels; NCH = 16-channel chunks per lane half
 // (8: slices of 256 input channels; 4: slices of 128 -- the q / k / v / merge projections, several of them in one launch)
 constexpr int w16_img(int NCH) { return 2 * (2 * NCH) * 2 * 128; }
-
-__device__ __forceinline__ unsigned int cvt_pk_f16w(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void split2x2w(float x0, float x1, unsigned int &hw, unsigned int &lw) {
-    hw = cvt_pk_f16w(x0, x1);
-    const f16x2w h = __builtin_bit_cast(f16x2w, hw);
-    lw = cvt_pk_f16w(x0 - (float)h.x, x1 - (float)h.y);
-}
-__device__ __forceinline__ int scale_exp_w(float mx, int none) {      // 2^e * mx in [2^11, 2^12)
-    const int fld = (int)(__float_as_uint(mx) >> 23);
-    const int ex = fld == 0 ? none : fld == 255 ? 0 : 138 - fld;
-    return min(max(ex, -100), 100);
-}
-__device__ __forceinline__ float pow2i_w(int e) { return __uint_as_float((unsigned int)(127 + e) << 23); }
 
 struct Ws16Args {
     const float *xa, *xb;          // token rows read by lane half 0 / 1 (slice 0): 128 channels each
@@ -113,16 +93,16 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
         float mx = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) mx = fmaxf(mx, fmaxf(fmaxf(fabsf(r[q].x), fabsf(r[q].y)), fmaxf(fabsf(r[q].z), fabsf(r[q].w))));
-        return scale_exp_w(fmaxf(mx, __shfl_xor(mx, 32, 64)), 100);       // the token's two channel halves sit 32 lanes apart
+        return sp16_scale_exp(fmaxf(mx, __shfl_xor(mx, 32, 64)), 100);       // the token's two channel halves sit 32 lanes apart
     };
     auto split_x = [&](const float4 (&r)[4], float sc, uint4 (&f)[2][2]) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             unsigned int h[4], l[4];
-            split2x2w(r[2 * s].x * sc, r[2 * s].y * sc, h[0], l[0]);
-            split2x2w(r[2 * s].z * sc, r[2 * s].w * sc, h[1], l[1]);
-            split2x2w(r[2 * s + 1].x * sc, r[2 * s + 1].y * sc, h[2], l[2]);
-            split2x2w(r[2 * s + 1].z * sc, r[2 * s + 1].w * sc, h[3], l[3]);
+            sp16_split2x2(r[2 * s].x * sc, r[2 * s].y * sc, h[0], l[0]);
+            sp16_split2x2(r[2 * s].z * sc, r[2 * s].w * sc, h[1], l[1]);
+            sp16_split2x2(r[2 * s + 1].x * sc, r[2 * s + 1].y * sc, h[2], l[2]);
+            sp16_split2x2(r[2 * s + 1].z * sc, r[2 * s + 1].w * sc, h[3], l[3]);
             f[s][0] = make_uint4(h[0], h[1], h[2], h[3]);
             f[s][1] = make_uint4(l[0], l[1], l[2], l[3]);
         }
@@ -132,7 +112,7 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
     fetch(xp, 1, raw[1]);
     fetch(xp, 2, raw[2]);
     int e_cur = chunk_max(raw[0]), e_nxt = e_cur;  // per lane (= token): domain of its accumulators / scale of the fragments converted last
-    split_x(raw[0], pow2i_w(e_cur), fb[0]);
+    split_x(raw[0], sp16_pow2i(e_cur), fb[0]);
     const uint4 *wb = Ws + hl * 128 + nl;
     uint4 wf0[4][2], wf1[4][2];                    // W fragments of the even / odd K steps
     auto load_w = [&](int ks, uint4 (&wf)[4][2]) {
@@ -152,14 +132,14 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         auto mfma_step = [&](const uint4 (&wf)[4][2], const uint4 (&xf)[2]) {
-            const f16x8w xh = __builtin_bit_cast(f16x8w, xf[0]), xl = __builtin_bit_cast(f16x8w, xf[1]);
+            const f16x8 xh = __builtin_bit_cast(f16x8, xf[0]), xl = __builtin_bit_cast(f16x8, xf[1]);
             // small terms first; the four accumulators take turns, so no MFMA waits for the one issued just before it
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8w, wf[j][1]), xh, acc[j], 0, 0, 0);
+            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[j][1]), xh, acc[j], 0, 0, 0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8w, wf[j][0]), xl, acc[j], 0, 0, 0);
+            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[j][0]), xl, acc[j], 0, 0, 0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8w, wf[j][0]), xh, acc[j], 0, 0, 0);
+            for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[j][0]), xh, acc[j], 0, 0, 0);
         };
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -169,7 +149,7 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
             else fetch(xn, c + 3 - NCH, raw[(c + 3) & 3]);
             const int e_chunk = chunk_max(raw[(c + 1) & 3]);
             e_nxt = (c == NCH - 1) ? e_chunk : min(e_cur, e_chunk);       // a new tile starts its own running scale
-            const float sc = pow2i_w(e_nxt);
+            const float sc = sp16_pow2i(e_nxt);
             // W fragments double buffered in registers: the eight LDS reads of K step ks + 1 are issued under the MFMAs of step ks
             // (left to itself the compiler keeps ONE fragment register and waits out the LDS latency before every MFMA pair)
             load_w(2 * c + 1, wf1);

@@ -31,8 +31,7 @@ __device__ __forceinline__ void lc_softmax_flow(Score score, float *__restrict__
         sc[rep] = s;
         mx = fmaxf(mx, s);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    mx = wave_all_max(mx);
     float sum = 0.f, ex = 0.f, ey = 0.f;
 #pragma unroll
     for (int rep = 0; rep < 2; ++rep) {
@@ -397,8 +396,7 @@ __global__ __launch_bounds__(256) void local_attn_prop_kernel(const float *__res
         }
     }
     float mx = s;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    mx = wave_all_max(mx);
     float p = lane < NT ? expf(s - mx) : 0.f;
     float sum = p, ox = p * vx, oy = p * vy;
 #pragma unroll

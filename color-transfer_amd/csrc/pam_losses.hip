@@ -17,11 +17,10 @@
 // image's partials in a fixed order and counts the mask: deterministic, no atomics.  Counts that are zero stay zero: the division
 // (and its 0 / 0 = NaN, as in the reference) is the caller's.
 #include "ct_common.h"
+#include "ct_split16.h"      // f32x16
 
 namespace ct {
 namespace pl {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kCyTile = 64, kCyK = 32;
 constexpr int kCyLdA = 36;            // A chunk [64 rows][32 k] + 4: 16-byte rows, conflict-free 16-byte operand reads

@@ -42,12 +42,6 @@ constexpr int kPngHeaderBits = 17 + 19 * 3 + 258 * 4;
 constexpr unsigned int kAdlerMod = 65521u;
 constexpr unsigned int kStoredMax = 65535u;
 
-__device__ __forceinline__ unsigned int paeth(unsigned int a, unsigned int b, unsigned int c) {
-    const int p = (int)a + (int)b - (int)c;
-    const int pa = abs(p - (int)a), pb = abs(p - (int)b), pc = abs(p - (int)c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
 // the neighbours of byte `col` of a row of 3-byte pixels: left, up, up-left; zero outside the frame (prev == nullptr: row 0)
 __device__ __forceinline__ void neighbours(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev, unsigned int col, unsigned int &a,
                                            unsigned int &b, unsigned int &c) {

@@ -23,6 +23,7 @@
 // global store-then-load).  32 KB of LDS for rows up to CT_PNG_MAX_WIDTH pixels.
 #include "ct_common.h"
 #include "ct_inflate.h"
+#include "ct_png.h"        // paeth
 
 namespace ct {
 
@@ -141,14 +142,8 @@ __global__ __launch_bounds__(kWave) void png_inflate_kernel(const uint8_t *__res
 }
 
 // ---- unfilter -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned int paeth_predictor(unsigned int a, unsigned int b, unsigned int c) {
-    const int p = (int)a + (int)b - (int)c;
-    const int pa = abs(p - (int)a), pb = abs(p - (int)b), pc = abs(p - (int)c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);         // ties: a, then b, then c
-}
-
 __device__ __forceinline__ unsigned int unfilter_byte(unsigned int x, unsigned int a, unsigned int b, unsigned int c, int type) {
-    const unsigned int pred = type == 1 ? a : type == 2 ? b : type == 3 ? (a + b) >> 1 : type == 4 ? paeth_predictor(a, b, c) : 0u;
+    const unsigned int pred = type == 1 ? a : type == 2 ? b : type == 3 ? (a + b) >> 1 : type == 4 ? paeth(a, b, c) : 0u;
     return (x + pred) & 255u;
 }
 

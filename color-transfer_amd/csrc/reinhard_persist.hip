@@ -100,25 +100,6 @@ struct Args {
     unsigned long long *stamps;       // diagnostic builds (-DCT_RP_STAMPS): [grid][2 waves][batch + 1][8] s_memrealtime values
 };
 
-__device__ __forceinline__ double wave_sum(double v) {          // fixed-shape tree; valid in lane 0
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-// float32 sum over the wave with DPP row operations (fixed tree: shifts by 1, 2, 4, 8 inside the rows of 16 lanes, then the
-// row totals broadcast into the next rows): six v_add_f32 and no LDS traffic; the total is returned wave-uniform.  Accuracy:
-// six roundings of 6e-8 relative on a sum of 64 lanes x 8 pixels, unbiased -- 1e-10 on a mean over 2 M pixels.
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#define CT_DPP_ADD(ctrl, rmask) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rmask, 0xf, true))
-    CT_DPP_ADD(0x111, 0xf);      // row_shr:1
-    CT_DPP_ADD(0x112, 0xf);      // row_shr:2
-    CT_DPP_ADD(0x114, 0xf);      // row_shr:4
-    CT_DPP_ADD(0x118, 0xf);      // row_shr:8  -> lane 15 of every row holds its row's sum
-    CT_DPP_ADD(0x142, 0xa);      // row_bcast:15 into rows 1 and 3
-    CT_DPP_ADD(0x143, 0xc);      // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
-#undef CT_DPP_ADD
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 __device__ __forceinline__ uint64_t realtime() { return __builtin_amdgcn_s_memrealtime(); }     // 100 MHz
 constexpr uint64_t kSpinTicks = 200000000ull;                    // 2 s
 // Sticky per-device status (one copy of this variable per device: the code object is loaded on each): set when a bounded spin
@@ -515,7 +496,7 @@ __global__ __launch_bounds__(kWaves * kWave) void reinhard_persist_kernel(const 
                 if (tail > 0) tail_moments(reinterpret_cast<const T *>(a.reference) + ((size_t)p * a.n_pixels + n_full * kTilePixels) * 3, tail, kf, sc, w, lane);
 #pragma unroll
                 for (int m = 0; m < 6; ++m) {
-                    const float v = wave_sum_f32(sf[m]);
+                    const float v = wave_sum_f32(sf[m]);      // 64 lanes x 8 pixels; its six roundings cost 1e-10 on a mean over 2 M pixels
                     if (lane == 0) sc->red[par][w][6 + m] = (double)v + sc->side[w][m];
                 }
             }

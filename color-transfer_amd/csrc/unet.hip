@@ -90,8 +90,7 @@ __global__ __launch_bounds__(256) void se_scale_kernel(const float *__restrict__
     for (int j = wave; j < NSQ; j += 4) {                  // one wave per squeezed channel
         float s = 0.f;
         for (int c = lane; c < C; c += 64) s = fmaf(w_reduce[(size_t)j * C + c], mean[c], s);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        s = wave_sum(s);
         if (lane == 0) sq[j] = swishf(s + b_reduce[j]);
     }
     __syncthreads();

@@ -62,3 +62,17 @@ def test_switches_are_read_through_the_helper_only():
         for m in re.finditer(r"\benv_(?:int|str)\(\s*([^,)]*)", code):
             arg = m.group(1).strip()
             assert arg.startswith('"') or (fname == "ct_env.h" and arg == "const char *name"), "csrc/%s: env switch named by %r" % (fname, arg)
+
+
+def test_fp16_and_wave_primitives_have_one_copy():
+    """The fp16 two-piece primitives live in csrc/ct_split16.h and the DPP wave maximum in csrc/ct_wave.h, once: a kernel file
+    that grows a private copy again (a fix to one would not reach the others) fails here.  The three-MFMA product is written out
+    only where its MFMAs are interleaved with other work by hand."""
+    code = {fname: re.sub(r"//[^\n]*", "", src) for fname, src in _sources()}
+
+    def holders(text):
+        return sorted(fname for fname, c in code.items() if text in c)
+
+    assert holders("v_cvt_pk_f16_f32") == ["ct_split16.h"]
+    assert holders("CT_DPP_MAX") == ["ct_wave.h"]
+    assert holders("__builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh") == ["conv_split.hip", "conv_ws.hip", "ct_split16.h"]
