@@ -11,6 +11,7 @@
 // results are bitwise reproducible run to run (no float atomics).
 #include <atomic>
 
+#include "ct_linear_u8.h"
 #include "ct_metrics.h"
 #include "ct_moments.h"
 #include "ct_reinhard_persist.h"
@@ -530,6 +531,7 @@ size_t ct_workspace_bytes(int kind, int64_t n_pixels, int n_images) {
         case CT_WS_REINHARD: { const size_t a = ct::ws_bytes_for(2 * n_images), b = ct::rp::ws_bytes(n_pixels, n_images); return a > b ? a : b; }
         case CT_WS_REINHARD_PSNR: { const size_t a = ct::ws_bytes_reinhard_psnr(n_images), b = ct::rp::ws_bytes(n_pixels, n_images); return a > b ? a : b; }
         case CT_WS_REINHARD_PERSIST: return ct::rp::ws_bytes(n_pixels, n_images);
+        case CT_WS_MK_U8: return ct::ws_bytes_mk_u8(n_images);
         default: return 0;
     }
 }

@@ -15,21 +15,12 @@
 // What does not sit on the 16-byte grid (a total that is no multiple of 16, H*W % 4 != 0 in CHW, an odd base) goes through the
 // element-wise tail / fallback of the same rule.
 #include "ct_common.h"
+#include "ct_quant.h"     // quant_u8, pack4: the rule itself
 
 namespace ct {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned int quant_u8(float x) {
-    // fmaxf(NaN, 0) = 0 (the non-NaN operand); -0.0f * 255 rounds to -0.0f, which converts to 0
-    const float c = fminf(fmaxf(x, 0.0f), 1.0f);
-    return (unsigned int)__builtin_rintf(c * 255.0f);
-}
-
-__device__ __forceinline__ unsigned int pack4(unsigned int a, unsigned int b, unsigned int c, unsigned int d) {
-    return a | (b << 8) | (c << 16) | (d << 24);
-}
 
 // in / out 16-byte aligned: n_chunks runs of 16 elements, then (block 0) the n_tail < 16 elements after them
 __global__ __launch_bounds__(kBlock) void pack_hwc_kernel(const float *__restrict__ in, int64_t n_chunks, int n_tail, uint8_t *__restrict__ out) {

@@ -24,6 +24,7 @@ CT_ABI_VERSION = 9            # include/ct_hip.h: CT_ABI_VERSION; lib() refuses 
 CT_LAB_STATS_STRIDE = 8
 CT_RGB_STATS_STRIDE = 16
 CT_WS_LAB_STATS, CT_WS_RGB_MEANCOV, CT_WS_REINHARD, CT_WS_IDT, CT_WS_REINHARD_PSNR, CT_WS_REINHARD_PERSIST = 0, 1, 2, 3, 4, 5
+CT_WS_MK_U8 = 6
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int

@@ -1,11 +1,12 @@
 """Reinhard / MK / Xiao: Lab and RGB statistics, the affine maps, the fused and persistent Reinhard entries, the Lab mode."""
 import ctypes
 
+import numpy as np
 import torch
 
-from ._core import (CT_LAB_STATS_STRIDE, CT_RGB_STATS_STRIDE, CT_WS_LAB_STATS, CT_WS_REINHARD, CT_WS_REINHARD_PERSIST,
+from ._core import (CT_LAB_STATS_STRIDE, CT_RGB_STATS_STRIDE, CT_WS_LAB_STATS, CT_WS_MK_U8, CT_WS_REINHARD, CT_WS_REINHARD_PERSIST,
                     CT_WS_REINHARD_PSNR, CT_WS_RGB_MEANCOV, CtHipError, SIGNATURES, _as_batch, _c_i64, _c_int, _c_p,
-                    _c_sz, _ptr, _require_cuda, _stream, _suffix, check, lib, workspace)
+                    _c_sz, _ptr, _require_cuda, _stream, _suffix, _upload_small, check, lib, workspace)
 
 SIGNATURES.update({
     "ct_profile_events": (None, [_c_p, _c_p, _c_p, _c_p]),
@@ -33,6 +34,10 @@ SIGNATURES.update({
     "ct_affine3x3_f32_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
     "ct_affine3x3_f64_f64": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
     "ct_affine3x3_f32_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_rgb_meancov_u8": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_affine3x3_u8_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_affine3x3_u8_u8": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
+    "ct_mk_u8": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_sz, _c_p]),
 })
 
 CT_LAB_TABLE, CT_LAB_EXACT = 0, 1
@@ -77,15 +82,21 @@ def lab_stats(img):
     return stats
 
 
+def _suffix_u8(t):
+    """_suffix for the entries that also read or write bytes (rgb_meancov, affine3x3)"""
+    return "u8" if t.dtype == torch.uint8 else _suffix(t)
+
+
 def rgb_meancov(img):
     """np.mean + np.cov (ddof 1) per image: float64 [B, 16] = mean[3], cov[9], n, 0,0,0.
-    Replaces methods/linear.py:64-67,103-106."""
+    Replaces methods/linear.py:64-67,103-106.  A uint8 image stands for k / 255; its record comes from exact integer sums
+    (ct_rgb_meancov_u8: independent of the summation order and of the batch, exactly 0 for a constant frame)."""
     x, _ = _as_batch(img)
     _require_cuda(x)
     B, n = x.shape[0], x.shape[1] * x.shape[2]
     stats = torch.empty((B, CT_RGB_STATS_STRIDE), dtype=torch.float64, device=x.device)
     ws = workspace(CT_WS_RGB_MEANCOV, n, B, x.device)
-    fn = getattr(lib(), "ct_rgb_meancov_" + _suffix(x))
+    fn = getattr(lib(), "ct_rgb_meancov_" + _suffix_u8(x))
     check(fn(_ptr(x), n, B, _ptr(stats), _ptr(ws), ws.numel(), _stream()))
     return stats
 
@@ -211,7 +222,7 @@ def _check_out(out, x, family):
         raise CtHipError("out must be contiguous")
     if out.numel() != x.numel():
         raise CtHipError("out has %d elements, the input %d" % (out.numel(), x.numel()))
-    name = "ct_%s_%s_%s" % (family, _suffix(x), _suffix(out))
+    name = "ct_%s_%s_%s" % (family, _suffix_u8(x), _suffix_u8(out))
     if name not in SIGNATURES:
         raise CtHipError("no kernel for %s" % name)
     return name
@@ -224,21 +235,70 @@ def _check_records(t, batch, what):
         raise CtHipError("%s must be float64 [B >= %d, %d], got %s %s" % (what, batch, CT_RGB_STATS_STRIDE, t.dtype, tuple(t.shape)))
 
 
-def mk(target, reference, decomposition="MK", out_dtype=torch.float64, out=None):
-    """methods.linear.monge_kantorovitch_color_transfer on device tensors, B pairs per call, no host sync (ct_mk_*)."""
+def mk(target, reference, decomposition="MK", out_dtype=None, out=None, gt=None, psnr_out=None):
+    """methods.linear.monge_kantorovitch_color_transfer on device tensors, B pairs per call, no host sync (ct_mk_*).
+    out_dtype: float64 by default.  uint8 frames (the image is k / 255; ct_mk_u8): out_dtype float32 (default, unclipped) or uint8
+    (ct_hip.pack_u8's rule on the float32 result); with gt (uint8 frames of the same shape) the call also fills psnr_out, float64
+    [B, 2] = (mse, PSNR) of the clamped float32 result, and returns (out, psnr_out), like reinhard_persist."""
     x, _ = _as_batch(target)
     r, _ = _as_batch(reference)
     _require_cuda(x, r)
     if x.shape != r.shape or x.dtype != r.dtype:
         raise CtHipError("fused mk needs equal shapes/dtypes")
     B, n = x.shape[0], x.shape[1] * x.shape[2]
+    mode = {"MK": 0, "sqrt": 1, "cholesky": 2}[decomposition]
+    if x.dtype == torch.uint8:
+        return _mk_u8(target, x, r, B, n, mode, out_dtype, out, gt, psnr_out)
+    if gt is not None or psnr_out is not None:
+        raise CtHipError("mk computes the PSNR for uint8 frames only (gt / psnr_out with %s frames)" % x.dtype)
     if out is None:
-        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+        out = torch.empty(x.shape, dtype=out_dtype or torch.float64, device=x.device)
     name = _check_out(out, x, "mk")
     ws = workspace(CT_WS_REINHARD, n, B, x.device)
-    mode = {"MK": 0, "sqrt": 1, "cholesky": 2}[decomposition]
     check(getattr(lib(), name)(_ptr(x), _ptr(r), _ptr(out), n, B, mode, _ptr(ws), ws.numel(), _stream()))
     return out.view(target.shape)
+
+
+def _mk_u8(target, x, r, B, n, mode, out_dtype, out, gt, psnr_out):
+    """mk() for uint8 frames: every argument error is raised here, before the C call"""
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype or torch.float32, device=x.device)
+    _require_cuda(out)
+    if out.device != x.device:
+        raise CtHipError("out is on %s, the input on %s" % (out.device, x.device))
+    if out.numel() != x.numel():
+        raise CtHipError("out has %d elements, the input %d" % (out.numel(), x.numel()))
+    if out.dtype not in (torch.float32, torch.uint8):
+        raise CtHipError("mk on uint8 frames writes float32 or uint8, not %s" % out.dtype)
+    null = ctypes.c_void_p(0)
+    g = None
+    if gt is not None:
+        g, _ = _as_batch(gt)
+        _require_cuda(g)
+        if g.dtype != torch.uint8 or g.shape != x.shape:
+            raise CtHipError("gt must be uint8 frames of the images' shape, got %s %s" % (g.dtype, tuple(g.shape)))
+        if psnr_out is None:
+            psnr_out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+        _require_cuda(psnr_out)
+        if psnr_out.dtype != torch.float64 or psnr_out.numel() < 2 * B:
+            raise CtHipError("psnr_out must be float64 with >= 2*B elements")
+    elif psnr_out is not None:
+        raise CtHipError("psnr_out without gt")
+    ws = workspace(CT_WS_MK_U8, n, B, x.device)
+    f32, u8 = (_ptr(out), null) if out.dtype == torch.float32 else (null, _ptr(out))
+    check(lib().ct_mk_u8(_ptr(x), _ptr(r), _ptr(g) if g is not None else null, f32, u8, _ptr(psnr_out) if g is not None else null,
+                         n, B, mode, _ptr(ws), ws.numel(), _stream()))
+    o = out.view(tuple(target.shape))
+    return (o, psnr_out) if g is not None else o
+
+
+def upload_records(records, device):
+    """Host float64 [B, 16] records (affine3x3 coefficients made on the host) -> a device tensor without a blocking copy: through
+    the binding's ring of pinned slots, asynchronously on the current stream."""
+    records = np.ascontiguousarray(records, dtype=np.float64)
+    if records.ndim != 2 or records.shape[1] != CT_RGB_STATS_STRIDE:
+        raise CtHipError("records must be [B, %d], got %s" % (CT_RGB_STATS_STRIDE, records.shape))
+    return _upload_small(records, device)
 
 
 def mk_coef(stats_t, stats_r, decomposition="MK"):
@@ -254,15 +314,16 @@ def mk_coef(stats_t, stats_r, decomposition="MK"):
     return coef
 
 
-def affine3x3(img, coef, out_dtype=torch.float64, out=None):
+def affine3x3(img, coef, out_dtype=None, out=None):
     """out = (x - mu_t) @ A + mu_r per image; coef float64 [B,16] = A[9], mu_t[3], mu_r[3], 0.
-    Replaces methods/linear.py:80,122."""
+    Replaces methods/linear.py:80,122.  out_dtype: float64 by default; for a uint8 image (x = k / 255) float32 (default) or
+    uint8 (ct_hip.pack_u8's rule on the float32 result)."""
     x, _ = _as_batch(img)
     _require_cuda(x)
     B, n = x.shape[0], x.shape[1] * x.shape[2]
     _check_records(coef, B, "coef")
     if out is None:
-        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+        out = torch.empty(x.shape, dtype=out_dtype or (torch.float32 if x.dtype == torch.uint8 else torch.float64), device=x.device)
     name = _check_out(out, x, "affine3x3")
     check(getattr(lib(), name)(_ptr(x), _ptr(coef), _ptr(out), n, B, _stream()))
     return out.view(img.shape)

@@ -84,12 +84,19 @@ def mask_view(mask):
 METRICS = ("Test PSNR", "Test SSIM", "Test FSIM", "Test iCID")        # what test_step logs, in its order (methods/__init__.py:37-40)
 
 
+REINHARD_SPEC = "methods.linear.color_transfer_between_images"
+MK_SPEC = "methods.linear.monge_kantorovitch_color_transfer"
+XIAO_SPEC = "methods.linear.color_transfer_in_correlated_color_space"
+
+
 class Runner(torch.nn.Module):
-    def __init__(self, func_spec, metrics=None):
+    def __init__(self, func_spec, metrics=None, byte_groups=False):
         """func_spec: the reference's only argument (methods/__init__.py:12).  metrics (not in the reference): which of psnr, ssim,
         fsim, icid test_step computes -- default all four, like the reference; `psnr` alone lets the Reinhard transfer take its
-        fused uint8 entry (test_group)."""
+        fused uint8 entry (test_group).  byte_groups (not in the reference; `--model.byte_groups true`): with `psnr` alone, MK
+        (default decomposition) and Xiao take whole groups of uint8 frames as well, and predict_group hands out bytes."""
         super().__init__()
+        self.byte_groups = bool(byte_groups)
         specs = func_spec.split(".")
         module, func = ".".join(specs[:-1]), specs[-1]
         mod = importlib.import_module(module)
@@ -103,27 +110,41 @@ class Runner(torch.nn.Module):
         self._out = None
 
     def takes_groups(self):
-        """True when whole groups of uint8 frames can go through ONE fused call: the Reinhard transfer with PSNR as the only
-        metric (ct_reinhard_psnr_u8 reads the bytes; k / 255 and its gamma expansion come from tables inside the kernel)."""
-        return self.func_spec == "methods.linear.color_transfer_between_images" and self.metrics == ("psnr",)
+        """True when whole groups of uint8 frames go through test_group / predict_group, which needs PSNR as the only metric: the
+        Reinhard transfer (ONE fused call: ct_reinhard_psnr_u8 reads the bytes; k / 255 and its gamma expansion come from tables
+        inside the kernel) and, with byte_groups, MK in its default decomposition (ct_mk_u8) and Xiao (its pieces on bytes)."""
+        if self.metrics != ("psnr",):
+            return False
+        return self.func_spec == REINHARD_SPEC or (self.byte_groups and self.func_spec in (MK_SPEC, XIAO_SPEC))
 
     def test_group(self, group_u8, psnr_out):
         """group_u8: device uint8 [3 roles: target, reference, gt][k][H][W][3]; psnr_out: float64 [k, 2] rows of the caller's table,
         filled with (mse, PSNR) per frame -- Runner.test_step's clamp + piq.psnr (methods/__init__.py:30-32) for k frames in one
-        asynchronous call, nothing else on the stream."""
+        asynchronous call, nothing else on the stream.  byte_groups: MK is one ct_hip.mk call with gt; Xiao is its three pieces
+        (moments of the bytes, the host SVDs, the affine map on the bytes) and ct_hip.frame_psnr."""
         import ct_hip
         k = group_u8.shape[1]
         if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:
             self._out = torch.empty((k,) + tuple(group_u8.shape[2:]), dtype=torch.float32, device=group_u8.device)
-        ct_hip.reinhard_persist(group_u8[0], group_u8[1], gt=group_u8[2], out=self._out[:k], psnr_out=psnr_out)
-        return self._out[:k]
+        out = self._out[:k]
+        if self.func_spec == MK_SPEC:
+            ct_hip.mk(group_u8[0], group_u8[1], out=out, gt=group_u8[2], psnr_out=psnr_out)
+        elif self.func_spec == XIAO_SPEC:
+            self.func_cuda(group_u8[0], group_u8[1], out=out)
+            psnr_out.copy_(ct_hip.frame_psnr(out.clamp(0, 1), group_u8[2].float() / 255))
+        else:
+            ct_hip.reinhard_persist(group_u8[0], group_u8[1], gt=group_u8[2], out=out, psnr_out=psnr_out)
+        return out
 
     def predict_group(self, group_u8):
         """group_u8 as for test_group ([2 or 3 roles: target, reference(, gt)][k][H][W][3], gt is not read) -> the corrected frames,
         float32 [k][H][W][3], from ONE asynchronous call; the buffer is reused by the next call (stream order keeps a reader
-        on the same stream safe).  `utils.cli predict` packs them to bytes with ct_hip.pack_u8."""
+        on the same stream safe).  `utils.cli predict` packs them to bytes with ct_hip.pack_u8.  byte_groups (MK, Xiao): the
+        corrected frames as bytes already, uint8 [k][H][W][3], freshly allocated (the writer holds them until their download)."""
         import ct_hip
         k = group_u8.shape[1]
+        if self.func_spec != REINHARD_SPEC:
+            return self.func_cuda(group_u8[0], group_u8[1], out_dtype=torch.uint8)
         if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:
             self._out = torch.empty((k,) + tuple(group_u8.shape[2:]), dtype=torch.float32, device=group_u8.device)
         return ct_hip.reinhard_persist(group_u8[0], group_u8[1], out=self._out[:k])

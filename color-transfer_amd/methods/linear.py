@@ -142,19 +142,48 @@ def mk_matrix(target_cov, reference_cov, decomposition="MK"):
     return T
 
 
-def color_transfer_in_correlated_color_space_cuda(target, reference, out_dtype=torch.float64):
+def _xiao_u8(target, reference, out_dtype, out=None):
+    """Xiao for B pairs of uint8 frames ([H,W,3] or [B,H,W,3], the image is k / 255): exact integer moments on the device, ONE
+    device-to-host copy of the 2 B records, the host SVDs of xiao_matrix, one asynchronous upload of the B coefficient records, the affine
+    map on the bytes."""
+    st = ct_hip.rgb_meancov(target)
+    sr = ct_hip.rgb_meancov(reference)
+    s = torch.stack([st, sr]).cpu().numpy()                  # [2, B, 16]
+    coef = np.zeros((s.shape[1], 16), dtype=np.float64)
+    for b in range(s.shape[1]):
+        T = xiao_matrix(s[0, b, 3:12].reshape(3, 3), s[1, b, 3:12].reshape(3, 3))
+        coef[b, 0:9] = T.T.reshape(9)                        # reference: (x - mu) @ T.T + mu_r
+        coef[b, 9:12] = s[0, b, 0:3]
+        coef[b, 12:15] = s[1, b, 0:3]
+    return ct_hip.affine3x3(target, ct_hip.upload_records(coef, target.device), out_dtype=out_dtype, out=out)
+
+
+def color_transfer_in_correlated_color_space_cuda(target, reference, out_dtype=None, out=None):
+    """Device-resident Xiao transfer.  Float tensors: one [H,W,3] pair, float64 out by default.  uint8 tensors ([H,W,3] or
+    [B,H,W,3] pairs of one shape; the image is k / 255): out_dtype float32 (default) or uint8."""
+    if target.dtype == torch.uint8:
+        if reference.dtype != torch.uint8 or reference.dim() != target.dim() or (target.dim() == 4 and reference.shape[0] != target.shape[0]):
+            raise ct_hip.CtHipError("Xiao on uint8 frames needs uint8 references, as many as targets")
+        return _xiao_u8(target, reference, out_dtype or torch.float32, out)
     mt, ct_, mr, cr = _host_moments(target, reference)
     T = xiao_matrix(ct_, cr)
-    return _affine(target, T.T, mt, mr, out_dtype)     # reference: (x - mu) @ T.T + mu_r
+    return _affine(target, T.T, mt, mr, out_dtype or torch.float64)     # reference: (x - mu) @ T.T + mu_r
 
 
-def monge_kantorovitch_color_transfer_cuda(target, reference, decomposition="MK", out_dtype=torch.float64,
+def monge_kantorovitch_color_transfer_cuda(target, reference, decomposition="MK", out_dtype=None,
                                            host_algebra=False, out=None):
     """Device-resident MK transfer, [H,W,3] or [B,H,W,3] tensors.  By default the 3x3 algebra also runs on the device
     (ct_mk_coef_f64: no host synchronisation, batches of pairs per call); host_algebra=True reproduces the
-    reference's scipy/numpy calls literally (single pair)."""
+    reference's scipy/numpy calls literally (single pair).  out_dtype: float64 by default; uint8 tensors (the image is k / 255)
+    give float32 (default) or uint8."""
     if decomposition not in ("cholesky", "sqrt", "MK"):
         raise ValueError("Unknown decomposition, use either 'cholesky', 'sqrt', or 'MK'")
+    if target.dtype == torch.uint8:
+        if host_algebra:
+            raise ct_hip.CtHipError("host_algebra reproduces the reference on float frames; uint8 frames take the device algebra")
+        out_dtype = out_dtype or torch.float32
+    else:
+        out_dtype = out_dtype or torch.float64
     if not host_algebra:
         if target.shape == reference.shape:
             return ct_hip.mk(target, reference, decomposition, out_dtype=out_dtype, out=out)

@@ -443,7 +443,11 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
                 if grouped:
                     # uint8 frames in pinned groups: one upload, ONE transfer call, one pack and ONE download per group of k frames
                     for n, (ids, dev) in enumerate(prefetch_groups(frames, indices, device)):
-                        slot, u8 = pack(n, model.predict_group(dev), "hwc")
+                        frames_out = model.predict_group(dev)
+                        if frames_out.dtype == torch.uint8:     # --model.byte_groups: bytes already, freshly allocated (as views are)
+                            writer.submit(ids, frames_out)
+                            continue
+                        slot, u8 = pack(n, frames_out, "hwc")
                         downloaded[slot] = writer.submit(ids, u8)
                     return
                 for n, (f, sample) in enumerate(ctx.samples(frames, indices)):

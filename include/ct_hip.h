@@ -49,7 +49,8 @@ enum ct_workspace_kind {
     CT_WS_REINHARD = 2,  /* ct_reinhard_*:  n_images = batch (pairs)                    */
     CT_WS_IDT = 3,       /* ct_idt_*:       n_images = batch (pairs)                    */
     CT_WS_REINHARD_PSNR = 4, /* ct_reinhard_psnr_f32: n_images = batch (pairs)          */
-    CT_WS_REINHARD_PERSIST = 5 /* ct_reinhard_persist_f32 / ct_reinhard_psnr_u8: n_images = batch (pairs); 0 = frame size not supported */
+    CT_WS_REINHARD_PERSIST = 5, /* ct_reinhard_persist_f32 / ct_reinhard_psnr_u8: n_images = batch (pairs); 0 = frame size not supported */
+    CT_WS_MK_U8 = 6      /* ct_mk_u8:       n_images = batch (pairs)                    */
 };
 
 int ct_abi_version(void);
@@ -192,6 +193,34 @@ int ct_affine3x3_f64_f64(const double *in, const double *coef, double *out, int6
                          int batch, void *stream);
 int ct_affine3x3_f32_f32(const float *in, const double *coef, float *out, int64_t n_pixels,
                          int batch, void *stream);
+
+/* ---- A3 / A5 / a3 on uint8 frames (csrc/linear_u8.hip): the image is k / 255, the scale skimage.img_as_float and the datasets
+ * hand over (utils/data.py:84; utils/postprocess.py:138 is img_as_ubyte(mkct(img_as_float(..), img_as_float(..)).clip(0, 1))).
+ * Added under ABI 9.
+ *
+ * ct_rgb_meancov_u8: the record of ct_rgb_meancov_f32.  Per image the sums of k and of k_i k_j are unsigned 64-bit integers, so the
+ * record does not depend on the order of summation: bitwise reproducible, independent of the batch, and the covariance of a
+ * constant frame is exactly 0.  cov_ij = (N sum k_i k_j - sum k_i sum k_j) / (N (N - 1)) / 255^2: the numerator exact in 128-bit
+ * integers, three roundings (its conversion to double, the two divisions); mean_i = sum k_i / (255 N), one rounding.
+ * n_pixels <= 94 906 265 (N (N - 1) <= 2^53, an exact double), else CT_E_BADARG; n_pixels < 2 gives the NaN of np.cov, like the
+ * _f32 entry; ws: ct_workspace_bytes(CT_WS_RGB_MEANCOV, n_pixels, n_images).                                               */
+int ct_rgb_meancov_u8(const uint8_t *rgb, int64_t n_pixels, int n_images, double *stats, void *ws, size_t ws_bytes,
+                      void *stream);
+/* ct_affine3x3_u8_*: x = (double)k / 255.0, then the arithmetic of ct_affine3x3_f64_f64 on x (the same fma order), rounded once to
+ * float32: bitwise (float)ct_affine3x3_f64_f64(k / 255.0).  The _u8 form then applies ct_pack_u8_f32's rule to that float32 value
+ * (rint(clamp(x, 0, 1) * 255), ties to even, NaN gives 0).                                                                    */
+int ct_affine3x3_u8_f32(const uint8_t *in, const double *coef, float *out, int64_t n_pixels, int batch, void *stream);
+int ct_affine3x3_u8_u8(const uint8_t *in, const double *coef, uint8_t *out, int64_t n_pixels, int batch, void *stream);
+/* ct_mk_u8: monge_kantorovitch_color_transfer (methods/linear.py:85-124) for `batch` pairs of uint8 frames in four stream-ordered
+ * launches: the moments of all 2 * batch images, their finishing launch, ct_mk_coef_f64, the apply sweep.  Bitwise the composition
+ * ct_rgb_meancov_u8 -> ct_mk_coef_f64 -> ct_affine3x3_u8_*.  out_f32 (unclipped) and out_u8 are each optional; both NULL:
+ * CT_E_BADARG.  With gt (uint8 frames like the images) and psnr_out, also psnr_out[i] = {mse, 10 log10(1 / mse)} like
+ * ct_reinhard_psnr_u8: the float32 result clamped to [0,1] against gt as float32 k / 255 (IEEE float32 division), differences
+ * formed and summed in float64 in a fixed order by the apply sweep while it writes (a fifth, one-workgroup launch finishes them;
+ * the result is not read back).  A NaN result (constant target) gives mse = NaN.  gt == NULL: no metric, psnr_out unused.
+ * ws: ct_workspace_bytes(CT_WS_MK_U8, n_pixels, batch).                                                                     */
+int ct_mk_u8(const uint8_t *target, const uint8_t *reference, const uint8_t *gt, float *out_f32, uint8_t *out_u8,
+             double *psnr_out, int64_t n_pixels, int batch, int decomposition, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- regrain: the second half of methods.iterative.automated_color_grading (methods/iterative.py:62-138) ----------------
  * img_in (the original target), img_col (the IDT result), out: device [height][width][3] float64, one frame per call; out
