@@ -16,7 +16,15 @@
 //   * counts are integers (LDS + global integer atomics) -> order independent;
 //   * LUT and interpolation use IEEE float64 division and separate multiply/add like numpy.
 // Hence bin indices, counts, LUTs AND the float64 output are bitwise identical to the oracle.
+//
+// ct_idt_u8 (uint8 frames in; float64, float32 and / or bytes out, + PSNR) runs the same kernels instantiated for uint8_t: a byte
+// is looked up in a 256-entry float64 table (which of two images it stands for: idt_fill_table) and then takes the statements
+// above, so the byte entry is bitwise the float entry on that image.  Its last apply sweep (idt_apply_kernel<., true>) writes the
+// requested outputs and the squared-error partials of the metric instead of (or besides) the float64 working image.
+#include "ct_bytes.h"
 #include "ct_common.h"
+#include "ct_metrics.h"
+#include "ct_quant.h"
 
 namespace ct {
 
@@ -36,6 +44,46 @@ __device__ __forceinline__ double key_f64(unsigned long long k) {
 
 __device__ __forceinline__ double proj(const double *r, double x0, double x1, double x2) {
     return fma(r[2], x2, fma(r[1], x1, r[0] * x0));
+}
+
+// ---- uint8 frames (ct_idt_u8) ----------------------------------------------------------------------------------------------
+// The bytes stand for one of two float64 images, chosen per call: entry k of a 256-entry table in LDS is
+// (double)((float)k / 255.0f) (input_f32: the float32 tensor the Runner makes of a frame) or (double)k / 255.0 (img_as_float).
+// Every sweep below is the float sweep's statements on that table's values, so the byte entry is bitwise the float entry.
+template <typename T> struct IsU8 { static constexpr bool v = false; };
+template <> struct IsU8<uint8_t> { static constexpr bool v = true; };
+
+// by the first 256 threads of the workgroup; the caller's next barrier publishes it
+__device__ __forceinline__ void idt_fill_table(double *tab, int input_f32) {
+    if (threadIdx.x < 256) tab[threadIdx.x] = input_f32 ? (double)((float)threadIdx.x / 255.0f) : (double)threadIdx.x / 255.0;
+}
+
+// fn(i, x0, x1, x2) for the pixels of one image that this thread takes in a grid of NT-thread workgroups.  Float images: one
+// pixel per thread and pass.  uint8: a thread takes runs of 16 pixels as three 16-byte loads (ct_bytes.h); the pixels in front
+// of the first run and behind the last go one per thread of workgroup 0.
+template <typename T, int NT, typename F>
+__device__ __forceinline__ void idt_sweep(const T *p, int64_t n, const double *tab, F &&fn) {
+    if constexpr (IsU8<T>::v) {
+        const int h = head_pixels(p, n);
+        const int64_t n_runs = (n - h) >> 4;
+        const uint8_t *body = p + 3 * h;
+        for (int64_t c = (int64_t)blockIdx.x * NT + threadIdx.x; c < n_runs; c += (int64_t)gridDim.x * NT) {
+            unsigned int w[12];
+            load48(body + c * 48, w);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) fn(h + (c << 4) + k, tab[byte_of(w, 3 * k)], tab[byte_of(w, 3 * k + 1)], tab[byte_of(w, 3 * k + 2)]);
+        }
+        if (blockIdx.x == 0) {
+            const int tail = (int)(n - h - (n_runs << 4));
+            if ((int)threadIdx.x < h + tail) {
+                const int64_t i = (int)threadIdx.x < h ? (int64_t)threadIdx.x : (n_runs << 4) + threadIdx.x;
+                fn(i, tab[p[3 * i]], tab[p[3 * i + 1]], tab[p[3 * i + 2]]);
+            }
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT)
+            fn(i, (double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2]);
+    }
 }
 
 // per (pair, iteration) workspace record, all zero-initialised by one zeroing launch per call (ct_common.h: zero_async)
@@ -90,9 +138,15 @@ static IdtLayout idt_layout(void *ws, int batch, int n_iter, int bins) {
 template <typename T, int MAXROT>
 __global__ __launch_bounds__(kIdtBlock) void idt_minmax_kernel(const T *__restrict__ tgt_img, int64_t n_tgt, const T *__restrict__ ref_img,
                                                                int64_t n_ref, const double *__restrict__ rot, int n_iter,
-                                                               unsigned long long *__restrict__ mm) {
+                                                               unsigned long long *__restrict__ mm, int input_f32) {
     constexpr int RG = 4;               // rotations per sweep
+    constexpr bool U8 = IsU8<T>::v;
     __shared__ unsigned long long lds[4 * 6 * RG];
+    __shared__ double tab[U8 ? 256 : 1];
+    if constexpr (U8) {
+        idt_fill_table(tab, input_f32);
+        __syncthreads();
+    }
     const int b = blockIdx.y;
     const int which = blockIdx.z;
     const T *img = which ? ref_img : tgt_img;
@@ -124,17 +178,21 @@ __global__ __launch_bounds__(kIdtBlock) void idt_minmax_kernel(const T *__restri
                     bad = fma(d, 0.0, bad);          // stays 0 unless d is NaN or infinite
                 }
         };
-        for (int64_t c = (int64_t)blockIdx.x * kIdtBlock + threadIdx.x; c < n_chunks; c += (int64_t)gridDim.x * kIdtBlock) {
-            Raw12<T> raw;
-            load12_raw<T>(p + c * 12, vec, raw);
-            double v[12];
-            unpack12<T>(raw, v);
+        if constexpr (U8) {
+            idt_sweep<T, kIdtBlock>(p, n, tab, [&](int64_t, double x0, double x1, double x2) { pixel(x0, x1, x2); });
+        } else {
+            for (int64_t c = (int64_t)blockIdx.x * kIdtBlock + threadIdx.x; c < n_chunks; c += (int64_t)gridDim.x * kIdtBlock) {
+                Raw12<T> raw;
+                load12_raw<T>(p + c * 12, vec, raw);
+                double v[12];
+                unpack12<T>(raw, v);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) pixel(v[3 * e], v[3 * e + 1], v[3 * e + 2]);
-        }
-        if (blockIdx.x == 0) {          // ragged tail: n % 4 pixels
-            const int64_t i = (n_chunks << 2) + threadIdx.x;
-            if (threadIdx.x < 3 && i < n) pixel((double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2]);
+                for (int e = 0; e < 4; ++e) pixel(v[3 * e], v[3 * e + 1], v[3 * e + 2]);
+            }
+            if (blockIdx.x == 0) {          // ragged tail: n % 4 pixels
+                const int64_t i = (n_chunks << 2) + threadIdx.x;
+                if (threadIdx.x < 3 && i < n) pixel((double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2]);
+            }
         }
         // keys: k[q][2j] = key(-min), k[q][2j+1] = key(max); a poisoned lane publishes NaN for all of them
         unsigned long long k[RG][6];
@@ -253,9 +311,12 @@ template <typename TT, typename TR>
 __global__ __launch_bounds__(kIdtHistBlock) void idt_hist_kernel(const TT *__restrict__ tgt, int64_t n_t, const TR *__restrict__ ref,
                                                              int64_t n_r, const double *__restrict__ rot,
                                                              const unsigned long long *__restrict__ mm, int n_iter, int it, int bins,
-                                                             unsigned int *__restrict__ hist, unsigned short *__restrict__ binidx) {
+                                                             unsigned int *__restrict__ hist, unsigned short *__restrict__ binidx,
+                                                             int input_f32) {
     extern __shared__ unsigned int lh[];  // [2][3][bins]
     __shared__ unsigned long long kstage[kMmShards * 12], keys[12];
+    __shared__ double tab[(IsU8<TT>::v || IsU8<TR>::v) ? 256 : 1];
+    if constexpr (IsU8<TT>::v || IsU8<TR>::v) idt_fill_table(tab, input_f32);   // published by the barriers of idt_reduce_keys
     const int b = blockIdx.y;
     for (int i = threadIdx.x; i < 6 * bins; i += kIdtHistBlock) lh[i] = 0;
     double r[9], lo[3], hi[3], step[3], scale[3];
@@ -267,26 +328,23 @@ __global__ __launch_bounds__(kIdtHistBlock) void idt_hist_kernel(const TT *__res
         idt_params(keys, j, bins, lo[j], hi[j], step[j], scale[j]);
     }
     __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * kIdtHistBlock;
     const TT *pt = tgt + (size_t)b * n_t * 3;
-    for (int64_t i = (int64_t)blockIdx.x * kIdtHistBlock + threadIdx.x; i < n_t; i += stride) {
-        const double x0 = (double)pt[3 * i], x1 = (double)pt[3 * i + 1], x2 = (double)pt[3 * i + 2];
+    idt_sweep<TT, kIdtHistBlock>(pt, n_t, tab, [&](int64_t i, double x0, double x1, double x2) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int k = idt_bin(proj(r + 3 * j, x0, x1, x2), bins, lo[j], hi[j], step[j], scale[j]);
             atomicAdd(&lh[j * bins + k], 1u);
             if (binidx) binidx[(((size_t)b * n_iter + it) * 3 + j) * n_t + i] = (unsigned short)k;
         }
-    }
+    });
     const TR *pr = ref + (size_t)b * n_r * 3;
-    for (int64_t i = (int64_t)blockIdx.x * kIdtHistBlock + threadIdx.x; i < n_r; i += stride) {
-        const double x0 = (double)pr[3 * i], x1 = (double)pr[3 * i + 1], x2 = (double)pr[3 * i + 2];
+    idt_sweep<TR, kIdtHistBlock>(pr, n_r, tab, [&](int64_t, double x0, double x1, double x2) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int k = idt_bin(proj(r + 3 * j, x0, x1, x2), bins, lo[j], hi[j], step[j], scale[j]);
             atomicAdd(&lh[(3 + j) * bins + k], 1u);
         }
-    }
+    });
     __syncthreads();
     unsigned int *gh = hist + (((size_t)b * n_iter + it) * kHistShards + (blockIdx.x % kHistShards)) * 6 * bins;
     for (int i = threadIdx.x; i < 6 * bins; i += kIdtHistBlock) {
@@ -401,22 +459,57 @@ __global__ __launch_bounds__(kIdtBlock) void idt_lut_kernel(const unsigned int *
 // A9 (+ next iteration's A6): d_r = interp(d0r, edges[1:], f, left=0); t += rinv @ (d_r - d0r)
 // grid = (G, batch); dynamic LDS = 3*bins*16 B
 // -------------------------------------------------------------------------------------------
-template <typename TT>
+// What the LAST apply sweep of ct_idt_u8 writes besides (or instead of) the float64 image: the result rounded once to float32,
+// its bytes by ct_quant.h's rule, and per workgroup one float64 partial sum of (clamp(float32 result, 0, 1) - gt)^2, gt as
+// float32 k / 255 (IEEE division), added per thread in pixel order and then by block_sum's fixed tree.
+struct IdtSinks {
+    float *f32;          // [batch][n_t][3] or NULL
+    uint8_t *u8;         // [batch][n_t][3] or NULL
+    const uint8_t *gt;   // [batch][n_t][3] or NULL
+    double *sq;          // [batch][kMaxBlocksPerImage], written when gt is given
+};
+
+constexpr int kIdtTilePx = 256;                  // pixels of one wave's tile: 768 bytes = 48 16-byte vectors
+constexpr int kIdtTileBytes = 3 * kIdtTilePx;
+
+// one wave's LDS traffic becomes visible to all of its lanes (LDS operations of a wave complete in order)
+__device__ __forceinline__ void idt_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// TT = float / double, LAST = false: the sweep of ct_idt_f32 / ct_idt_f64, one pixel per thread and pass.
+// TT = uint8_t or LAST = true (ct_idt_u8): a wave takes tiles of 256 pixels on the 16-byte grid of the frame's bytes.  The tile's
+// target bytes (and ground-truth bytes) come in as 16-byte loads into the wave's LDS buffer, lane l then owns pixels l, l + 64,
+// l + 128, l + 192 of the tile -- so the float64 and float32 stores of a wave are contiguous, never a long run per lane -- and
+// the result bytes go back through the same buffer and out as 16-byte stores.  The pixels in front of the first tile and behind
+// the last take the same arithmetic one by one in workgroup 0.  LAST stores the float64 image only when `out` is given.
+template <typename TT, bool LAST>
 __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restrict__ tgt, double *__restrict__ out, int64_t n_t,
                                                               const double *__restrict__ rot, const double *__restrict__ rinv,
                                                               const double *__restrict__ lut,
                                                               int n_iter, int it, int bins, int round_f32,
-                                                              unsigned long long *__restrict__ mm) {
+                                                              unsigned long long *__restrict__ mm, int input_f32, IdtSinks sk) {
+    constexpr bool U8 = IsU8<TT>::v;
+    constexpr bool TILED = U8 || LAST;
     extern __shared__ double2 sl[];  // [3][bins] (f, slope)
     __shared__ unsigned long long lds[4 * 6];
     __shared__ unsigned long long kstage[kMmShards * 12], keys[12];
+    __shared__ double tab[U8 ? 256 : 1];
+    __shared__ float tabf[LAST ? 256 : 1];
+    __shared__ double red[4];
+    __shared__ __attribute__((aligned(16))) uint8_t iob[TILED ? 4 * kIdtTileBytes : 16];   // per wave: target bytes in, result bytes out
+    __shared__ __attribute__((aligned(16))) uint8_t gtb[LAST ? 4 * kIdtTileBytes : 16];    // per wave: ground-truth bytes
     const int b = blockIdx.y;
     {
         const double2 *g = reinterpret_cast<const double2 *>(lut + ((size_t)b * n_iter + it) * 3 * bins * 2);
         for (int i = threadIdx.x; i < 3 * bins; i += kIdtBlock) sl[i] = g[i];
     }
+    if constexpr (U8) idt_fill_table(tab, input_f32);                       // published by the barriers of idt_reduce_keys
+    if constexpr (LAST) tabf[threadIdx.x] = (float)threadIdx.x / 255.0f;    // kIdtBlock == 256: one entry per thread
     double r[9], ri[9], rn[9], lo[3], hi[3], step[3], scale[3];
-    const bool has_next = (it + 1 < n_iter);
+    const bool has_next = !LAST && (it + 1 < n_iter);
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
         r[i] = rot[((size_t)b * n_iter + it) * 9 + i];
@@ -433,10 +526,11 @@ __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restri
     // and the order-preserving key four more integer ops: ~50 instructions per pixel in round 2); the keys the integer
     // atomicMax needs are built once per lane at the end, like in idt_minmax_kernel, non-finite projections poison the range
     double nmn[3] = {INFINITY, INFINITY, INFINITY}, nmx[3] = {-INFINITY, -INFINITY, -INFINITY}, bad = 0.0;
-    const TT *p = tgt + (size_t)b * n_t * 3;
-    double *o = out + (size_t)b * n_t * 3;
-    for (int64_t i = (int64_t)blockIdx.x * kIdtBlock + threadIdx.x; i < n_t; i += (int64_t)gridDim.x * kIdtBlock) {
-        const double x0 = (double)p[3 * i], x1 = (double)p[3 * i + 1], x2 = (double)p[3 * i + 2];
+    const size_t off = (size_t)b * n_t * 3;
+    const TT *p = tgt + off;
+    double *o = (!LAST || out) ? out + off : nullptr;
+    // pixel i: x -> y, the float64 store and the next iteration's lo / hi
+    auto pixel = [&](int64_t i, double x0, double x1, double x2, double &y0, double &y1, double &y2) {
         double delta[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -456,10 +550,10 @@ __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restri
             if (round_f32) dr = (double)(float)dr;   // reference: d_r is float32 on iteration 0 for float32 input
             delta[j] = dr - x;
         }
-        const double y0 = proj(ri + 0, delta[0], delta[1], delta[2]) + x0;
-        const double y1 = proj(ri + 3, delta[0], delta[1], delta[2]) + x1;
-        const double y2 = proj(ri + 6, delta[0], delta[1], delta[2]) + x2;
-        o[3 * i] = y0; o[3 * i + 1] = y1; o[3 * i + 2] = y2;
+        y0 = proj(ri + 0, delta[0], delta[1], delta[2]) + x0;
+        y1 = proj(ri + 3, delta[0], delta[1], delta[2]) + x1;
+        y2 = proj(ri + 6, delta[0], delta[1], delta[2]) + x2;
+        if (!LAST || o) { o[3 * i] = y0; o[3 * i + 1] = y1; o[3 * i + 2] = y2; }
         if (has_next) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
@@ -468,6 +562,103 @@ __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restri
                 nmx[j] = fmax(nmx[j], d);
                 bad = fma(d, 0.0, bad);              // stays 0 unless d is NaN or infinite
             }
+        }
+    };
+    if constexpr (!TILED) {
+        for (int64_t i = (int64_t)blockIdx.x * kIdtBlock + threadIdx.x; i < n_t; i += (int64_t)gridDim.x * kIdtBlock) {
+            double y0, y1, y2;
+            pixel(i, (double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2], y0, y1, y2);
+        }
+    } else {
+        float *of = (LAST && sk.f32) ? sk.f32 + off : nullptr;
+        uint8_t *o8 = (LAST && sk.u8) ? sk.u8 + off : nullptr;
+        const uint8_t *g = (LAST && sk.gt) ? sk.gt + off : nullptr;
+        double acc[1] = {0.0};
+        auto sqerr = [&](float v, unsigned int kgt) {
+            const float c = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+            const double d = (double)c - (double)tabf[kgt];
+            acc[0] += d * d;
+        };
+        // the tiles start on the 16-byte grid of a buffer whose base is aligned; a buffer that is not takes byte accesses
+        const int h = head_pixels((uintptr_t)off, n_t);
+        const int64_t n_tiles = (n_t - h) / kIdtTilePx;
+        const int64_t e_body = 3 * (int64_t)h;
+        const bool vin = U8 && (reinterpret_cast<uintptr_t>(p + e_body) & 15) == 0;
+        const bool v8 = o8 && (reinterpret_cast<uintptr_t>(o8 + e_body) & 15) == 0;
+        const bool vg = g && (reinterpret_cast<uintptr_t>(g + e_body) & 15) == 0;
+        const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
+        uint8_t *wio = iob + wid * kIdtTileBytes, *wgt = gtb + (LAST ? wid * kIdtTileBytes : 0);
+        for (int64_t t = (int64_t)blockIdx.x * (kIdtBlock / kWave) + wid; t < n_tiles; t += (int64_t)gridDim.x * (kIdtBlock / kWave)) {
+            const int64_t px0 = h + t * kIdtTilePx, e0 = 3 * px0;
+            if constexpr (U8) {
+                const uint8_t *src = reinterpret_cast<const uint8_t *>(p) + e0;
+                if (vin) {
+                    if (lane < kIdtTileBytes / 16) reinterpret_cast<uint4 *>(wio)[lane] = reinterpret_cast<const uint4 *>(src)[lane];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) wio[j * 64 + lane] = src[j * 64 + lane];
+                }
+            }
+            if (LAST && g) {
+                if (vg) {
+                    if (lane < kIdtTileBytes / 16) reinterpret_cast<uint4 *>(wgt)[lane] = reinterpret_cast<const uint4 *>(g + e0)[lane];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) wgt[j * 64 + lane] = g[e0 + j * 64 + lane];
+                }
+            }
+            idt_wave_sync();
+#pragma unroll
+            for (int k = 0; k < kIdtTilePx / kWave; ++k) {
+                const int q = 3 * (k * kWave + lane);                      // this lane's pixel inside the tile, in elements
+                const int64_t i = px0 + k * kWave + lane;
+                double x0, x1, x2, y0, y1, y2;
+                if constexpr (U8) { x0 = tab[wio[q]]; x1 = tab[wio[q + 1]]; x2 = tab[wio[q + 2]]; }
+                else { x0 = (double)p[3 * i]; x1 = (double)p[3 * i + 1]; x2 = (double)p[3 * i + 2]; }
+                pixel(i, x0, x1, x2, y0, y1, y2);
+                if constexpr (LAST) {
+                    const float v[3] = {(float)y0, (float)y1, (float)y2};
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        if (of) of[3 * i + j] = v[j];
+                        if (o8) wio[q + j] = (uint8_t)quant_u8(v[j]);
+                        if (g) sqerr(v[j], wgt[q + j]);
+                    }
+                }
+            }
+            idt_wave_sync();
+            if (LAST && o8) {
+                if (v8) {
+                    if (lane < kIdtTileBytes / 16) reinterpret_cast<uint4 *>(o8 + e0)[lane] = reinterpret_cast<const uint4 *>(wio)[lane];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) o8[e0 + j * 64 + lane] = wio[j * 64 + lane];
+                }
+            }
+            idt_wave_sync();                                               // the next tile overwrites the buffers
+        }
+        if (blockIdx.x == 0) {
+            const int64_t done = h + n_tiles * kIdtTilePx, n_rest = h + (n_t - done);   // < 16 + 256 + 16
+            for (int64_t rr = threadIdx.x; rr < n_rest; rr += kIdtBlock) {
+                const int64_t i = rr < h ? rr : done + (rr - h);
+                double x0, x1, x2, y0, y1, y2;
+                if constexpr (U8) { x0 = tab[p[3 * i]]; x1 = tab[p[3 * i + 1]]; x2 = tab[p[3 * i + 2]]; }
+                else { x0 = (double)p[3 * i]; x1 = (double)p[3 * i + 1]; x2 = (double)p[3 * i + 2]; }
+                pixel(i, x0, x1, x2, y0, y1, y2);
+                if constexpr (LAST) {
+                    const float v[3] = {(float)y0, (float)y1, (float)y2};
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        if (of) of[3 * i + j] = v[j];
+                        if (o8) o8[3 * i + j] = (uint8_t)quant_u8(v[j]);
+                        if (g) sqerr(v[j], g[3 * i + j]);
+                    }
+                }
+            }
+        }
+        if (LAST && g) {                                                   // uniform over the grid
+            block_sum<1>(acc, red);
+            if (threadIdx.x == 0) sk.sq[(size_t)b * kMaxBlocksPerImage + blockIdx.x] = acc[0];
         }
     }
     if (has_next) {
@@ -480,10 +671,10 @@ __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restri
             key[2 * j + 1] = poisoned ? knan : f64_key(nmx[j]);
         }
 #pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) {
+        for (int off_ = kWave / 2; off_ > 0; off_ >>= 1) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
-                const unsigned long long ov = __shfl_down(key[i], off, kWave);
+                const unsigned long long ov = __shfl_down(key[i], off_, kWave);
                 key[i] = ov > key[i] ? ov : key[i];
             }
         }
@@ -532,10 +723,25 @@ static int idt_apply_grid(int64_t n, int batch) {
     return want < 1 ? 1 : (int)want;
 }
 
+// ct_idt_u8 only: which image the bytes stand for, where the float64 working image lives and what the last sweep writes
+struct IdtU8 {
+    int input_f32;
+    double *out_f64;     // or NULL: the working image is `state` and the last sweep does not store it
+    IdtSinks sinks;
+    double *psnr_out;
+};
+
+// the workspace of ct_idt_u8: idt_layout, then the squared-error partials, then (state_in_ws) the float64 working image
+static size_t idt_u8_sq_bytes(int batch) { return (size_t)batch * kMaxBlocksPerImage * sizeof(double); }
+static size_t idt_u8_state_bytes(int batch, int64_t n_t) { return ((size_t)batch * (size_t)n_t * 3 * sizeof(double) + 15) & ~(size_t)15; }
+
+// T = float / double: u8 == NULL, `out` is the result and the working image.  T = uint8_t: `out` is the working image
+// (u8->out_f64 or the workspace) and the last iteration's apply sweep is the LAST form.
 template <typename T>
 static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_r, int batch, const double *rot,
                     const double *rinv, int n_iter, int bins, int round_dr_f32, double *out, void *ws, size_t ws_bytes,
-                    const ct_idt_debug *dbg, void *stream_) {
+                    const ct_idt_debug *dbg, void *stream_, const IdtU8 *u8 = nullptr) {
+    constexpr bool U8 = IsU8<T>::v;
     hipStream_t s = (hipStream_t)stream_;
     if (n_t < 0 || n_r < 0 || batch < 0 || n_iter < 0 || bins < 1 || bins > kIdtMaxBins) return CT_E_BADARG;
     if (batch == 0) return CT_OK;
@@ -546,8 +752,11 @@ static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_
     hipError_t e;
     if (n_iter == 0) return CT_E_BADARG;   // the host returns the input untouched in that case
     if (n_t == 0) return CT_OK;
+    const int input_f32 = U8 ? u8->input_f32 : 0;
+    const IdtSinks no_sinks = {nullptr, nullptr, nullptr, nullptr};
     { const int zr = zero_async(ws, l.zero_bytes, s); if (zr) return zr; }
-    const int gt = idt_apply_grid(n_t, batch);
+    // the tiled sweeps (uint8 in, or the last one of ct_idt_u8) take 1024 pixels per workgroup and pass
+    const int gt = idt_apply_grid(n_t, batch), gt_tiled = idt_apply_grid(n_t / 4 + 1, batch);
     // the lo/hi sweeps end in 6 * rotations same-address 64-bit atomicMax per workgroup, which serialise in L2 (~20 ns each):
     // with 2048 workgroups that tail was 40 of the sweep's 45 us -- one workgroup per CU keeps it under 5 us
     const int gmm_t = idt_minmax_grid(n_t, batch), gmm_r = idt_minmax_grid(n_r, batch);
@@ -555,7 +764,7 @@ static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_
     {
         const int gmm = gmm_t > gmm_r ? gmm_t : gmm_r;
         hipLaunchKernelGGL((idt_minmax_kernel<T, 8>), dim3(gmm, batch, n_r > 0 ? 2 : 1), dim3(kIdtBlock), 0, s, target, n_t, reference, n_r, rot,
-                           n_iter, l.mm);
+                           n_iter, l.mm, input_f32);
         CT_CHECK_LAUNCH();
     }
     // the histogram flush is 6*bins global integer atomics per workgroup onto the SAME addresses: keep the grid at
@@ -571,25 +780,44 @@ static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_
         unsigned short *bi = (dbg && dbg->binidx) ? dbg->binidx : nullptr;
         if (it == 0) {
             hipLaunchKernelGGL((idt_hist_kernel<T, T>), dim3(gh, batch), dim3(kIdtHistBlock), 6 * bins * sizeof(unsigned int), s,
-                               target, n_t, reference, n_r, rot, l.mm, n_iter, it, bins, l.hist, bi);
+                               target, n_t, reference, n_r, rot, l.mm, n_iter, it, bins, l.hist, bi, input_f32);
         } else {
             hipLaunchKernelGGL((idt_hist_kernel<double, T>), dim3(gh, batch), dim3(kIdtHistBlock),
                                6 * bins * sizeof(unsigned int), s, (const double *)out, n_t, reference, n_r, rot, l.mm,
-                               n_iter, it, bins, l.hist, bi);
+                               n_iter, it, bins, l.hist, bi, input_f32);
         }
         CT_CHECK_LAUNCH();
         hipLaunchKernelGGL(idt_lut_kernel, dim3(3, batch), dim3(kIdtBlock), 3 * bins * sizeof(double) + 2 * bins * sizeof(unsigned int), s,
                            l.hist, l.mm, l.par, n_iter, it, bins, l.lut, l.hsum);
         CT_CHECK_LAUNCH();
         const int rf = (round_dr_f32 && it == 0) ? 1 : 0;
+        const size_t lds = 3 * bins * sizeof(double2);
+        if constexpr (U8) {
+            if (it == n_iter - 1) {         // the last sweep: the requested outputs and the metric partials
+                if (it == 0)
+                    hipLaunchKernelGGL((idt_apply_kernel<T, true>), dim3(gt_tiled, batch), dim3(kIdtBlock), lds, s, target, u8->out_f64, n_t,
+                                       rot, rinv, l.lut, n_iter, it, bins, rf, l.mm, input_f32, u8->sinks);
+                else
+                    hipLaunchKernelGGL((idt_apply_kernel<double, true>), dim3(gt_tiled, batch), dim3(kIdtBlock), lds, s, (const double *)out,
+                                       u8->out_f64, n_t, rot, rinv, l.lut, n_iter, it, bins, rf, l.mm, input_f32, u8->sinks);
+                CT_CHECK_LAUNCH();
+                continue;
+            }
+        }
         if (it == 0) {
-            hipLaunchKernelGGL((idt_apply_kernel<T>), dim3(gt, batch), dim3(kIdtBlock), 3 * bins * sizeof(double2), s, target,
-                               out, n_t, rot, rinv, l.lut, n_iter, it, bins, rf, l.mm);
+            hipLaunchKernelGGL((idt_apply_kernel<T, false>), dim3(U8 ? gt_tiled : gt, batch), dim3(kIdtBlock), lds, s, target,
+                               out, n_t, rot, rinv, l.lut, n_iter, it, bins, rf, l.mm, input_f32, no_sinks);
         } else {
-            hipLaunchKernelGGL((idt_apply_kernel<double>), dim3(gt, batch), dim3(kIdtBlock), 3 * bins * sizeof(double2), s,
-                               (const double *)out, out, n_t, rot, rinv, l.lut, n_iter, it, bins, rf, l.mm);
+            hipLaunchKernelGGL((idt_apply_kernel<double, false>), dim3(gt, batch), dim3(kIdtBlock), lds, s,
+                               (const double *)out, out, n_t, rot, rinv, l.lut, n_iter, it, bins, rf, l.mm, input_f32, no_sinks);
         }
         CT_CHECK_LAUNCH();
+    }
+    if constexpr (U8) {
+        if (u8->sinks.gt) {
+            const int rc = launch_psnr_finish(u8->sinks.sq, gt_tiled, n_t * 3, batch, u8->psnr_out, s);
+            if (rc) return rc;
+        }
     }
     if (dbg) {   // parity probes: device-to-device copies of the integer / LUT state
         if (dbg->hist &&
@@ -627,6 +855,38 @@ int ct_idt_f64(const double *target, int64_t n_t, const double *reference, int64
                const ct_idt_debug *dbg, void *stream) {
     return ct::idt_impl<double>(target, n_t, reference, n_r, batch, rot, rinv, n_iter, bins, round_dr_f32, out, ws, ws_bytes,
                                 dbg, stream);
+}
+
+size_t ct_idt_u8_workspace_bytes(int batch, int n_iter, int bins, int64_t n_t, int state_in_ws) {
+    if (n_t < 0) return 0;
+    const size_t base = ct_idt_workspace_bytes(batch, n_iter, bins);
+    if (base == 0 && batch != 0) return 0;
+    return base + ct::idt_u8_sq_bytes(batch) + (state_in_ws ? ct::idt_u8_state_bytes(batch, n_t) : 0);
+}
+
+int ct_idt_u8(const uint8_t *target, int64_t n_t, const uint8_t *reference, int64_t n_r, const uint8_t *gt, int batch,
+              const double *rot, const double *rinv, int n_iter, int bins, int input_f32, int round_dr_f32, double *out_f64,
+              float *out_f32, uint8_t *out_u8, double *psnr_out, void *ws, size_t ws_bytes, const ct_idt_debug *dbg, void *stream) {
+    if (n_t < 0 || n_r < 0 || batch < 0 || n_iter < 1 || bins < 1 || bins > ct::kIdtMaxBins) return CT_E_BADARG;
+    if (!out_f64 && !out_f32 && !out_u8) return CT_E_BADARG;
+    if (gt && batch > 0 && !psnr_out) return CT_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(out_f64) & 7) || (reinterpret_cast<uintptr_t>(out_f32) & 3) || (reinterpret_cast<uintptr_t>(psnr_out) & 7))
+        return CT_E_ALIGN;
+    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15)) return CT_E_WORKSPACE;
+    const size_t base = ct_idt_workspace_bytes(batch, n_iter, bins);
+    if (ws_bytes < ct_idt_u8_workspace_bytes(batch, n_iter, bins, n_t, out_f64 ? 0 : 1)) return CT_E_WORKSPACE;
+    char *w = reinterpret_cast<char *>(ws);
+    ct::IdtU8 u;
+    u.input_f32 = input_f32 ? 1 : 0;
+    u.out_f64 = out_f64;
+    u.sinks.f32 = out_f32;
+    u.sinks.u8 = out_u8;
+    u.sinks.gt = gt;
+    u.sinks.sq = reinterpret_cast<double *>(w + base);
+    u.psnr_out = psnr_out;
+    double *state = out_f64 ? out_f64 : reinterpret_cast<double *>(w + base + ct::idt_u8_sq_bytes(batch));
+    return ct::idt_impl<uint8_t>(target, n_t, reference, n_r, batch, rot, rinv, n_iter, bins, round_dr_f32, state, ws, ws_bytes, dbg,
+                                 stream, &u);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@ rotations are drawn on the host exactly like the reference does -- one
 (iterative.py:32) -- so a caller that seeds `np.random` gets the same matrices; everything per
 pixel runs in HIP kernels (libct_hip.so: ct_idt_f32 / ct_idt_f64).  Extra keyword `rotations=`
 lets a caller pass the matrices explicitly (used by the parity tests and by world-size
-independent frame sharding).  No CPU fallback.
+independent frame sharding).  No CPU fallback.  `iterative_distribution_transfer_cuda` also takes uint8 device frames
+(ct_idt_u8: bytes in, float64 / float32 / bytes out); `draw_group_rotations(k)` draws for k frames in the reference's order.
 
 `automated_color_grading(target, reference)` (iterative.py:118-138) = IDT followed by `_regrain` (iterative.py:62-117:
 multigrid gradient-preserving relaxation over a skimage.transform.resize pyramid), both on the device
@@ -21,7 +22,7 @@ import torch
 import ct_hip
 from methods.linear import _as_raw_float, _device
 
-__all__ = ["iterative_distribution_transfer", "automated_color_grading", "draw_rotations"]
+__all__ = ["iterative_distribution_transfer", "automated_color_grading", "draw_rotations", "draw_group_rotations"]
 
 
 def draw_rotations(n_iter, n_dims=3, seed=None):
@@ -34,8 +35,27 @@ def draw_rotations(n_iter, n_dims=3, seed=None):
     return np.stack([scipy.stats.special_ortho_group.rvs(n_dims) for _ in range(n_iter)])
 
 
-def iterative_distribution_transfer_cuda(target, reference, bins=255, n_iter=4, rotations=None, out=None):
-    """Device-resident IDT: CUDA tensors [H,W,3] / [B,H,W,3] in, float64 tensor out (asynchronous)."""
+def draw_group_rotations(k, n_iter=4):
+    """[k, n_iter, 3, 3]: the rotations of k frames, drawn from numpy's global RNG exactly as k successive draw_rotations(n_iter)
+    calls draw them -- the reference's per-sample order (methods/__init__.py:20-25, iterative.py:32)."""
+    if k == 0:
+        return np.zeros((0, n_iter, 3, 3))
+    return np.stack([draw_rotations(n_iter) for _ in range(k)])
+
+
+def iterative_distribution_transfer_cuda(target, reference, bins=255, n_iter=4, rotations=None, out=None, input_f32=True,
+                                         out_dtype=None):
+    """Device-resident IDT: CUDA tensors [H,W,3] / [B,H,W,3] in, float64 tensor out (asynchronous).  uint8 frames go to
+    ct_hip.idt_u8: the bytes stand for float32(k) / 255 (input_f32, what a Runner makes of a frame) or for k / 255.0, and the
+    result is float64 (default), float32 or bytes (out_dtype); without `rotations` a batch draws per frame, in frame order."""
+    if target.dtype == torch.uint8:
+        if rotations is None:
+            rotations = draw_group_rotations(target.shape[0], n_iter) if target.dim() == 4 else draw_rotations(n_iter)
+        if tuple(rotations.shape)[-3] == 0:
+            raise ValueError("iterative_distribution_transfer_cuda on uint8 frames needs n_iter >= 1")
+        return ct_hip.idt_u8(target, reference, rotations, bins=bins, input_f32=input_f32, out_dtype=out_dtype or torch.float64, out=out)
+    if out_dtype not in (None, torch.float64) or input_f32 is not True:
+        raise ValueError("input_f32 / out_dtype are for uint8 frames; float frames give float64")
     if rotations is None:
         rotations = draw_rotations(n_iter)
     if tuple(rotations.shape)[-3] == 0:             # n_iter = 0: the reference's loop body never runs

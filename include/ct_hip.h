@@ -323,6 +323,30 @@ int ct_idt_f64(const double *target, int64_t n_t, const double *reference, int64
                const double *rot, const double *rinv, int n_iter, int bins, int round_dr_f32,
                double *out, void *ws, size_t ws_bytes, const ct_idt_debug *dbg, void *stream);
 
+/* ct_idt_u8: the same transfer for `batch` pairs of uint8 frames (target [batch][n_t][3], reference [batch][n_r][3]), bytes in and
+ * float64, float32 and / or bytes out, through the kernels of ct_idt_f32 / ct_idt_f64 reading one 256-entry float64 table:
+ *   input_f32 = 1 : byte k stands for (double)((float)k / 255.0f), a correctly rounded float32 division -- the float32 tensor
+ *                   `frame / 255` that a Runner feeds to ct_idt_f32;
+ *   input_f32 = 0 : byte k stands for (double)k / 255.0 (img_as_float).
+ * With input_f32 = round_dr_f32 = 1 every probe of dbg and out_f64 are bitwise what ct_idt_f32 gives on float32(k) / 255, with
+ * input_f32 = round_dr_f32 = 0 bitwise what ct_idt_f64 gives on k / 255.0.  out_f32 is out_f64 rounded once; out_u8 is
+ * ct_pack_u8_f32's rule on that float32 value (rint(clamp(x, 0, 1) * 255), ties to even, NaN gives 0).  Each of the three
+ * outputs is optional, all three NULL: CT_E_BADARG.  Without out_f64 the float64 working image lives in the workspace
+ * (state_in_ws = 1: 24 bytes per pixel and pair) and the last apply sweep does not store it.
+ * With gt (uint8 [batch][n_t][3]) and psnr_out, also psnr_out[i] = {mse, 10 log10(1 / mse)} in ct_mk_u8's layout and by its
+ * rule: the float32 result clamped to [0,1] against gt as float32 k / 255 (IEEE float32 division), differences formed and summed
+ * in float64 in a fixed order by the last apply sweep while it writes, one partial per workgroup, finished by one more launch;
+ * the result is not read back.  A NaN result gives mse = NaN.  gt without psnr_out: CT_E_BADARG; gt == NULL: no metric.
+ * Plain stream-ordered launches.  n_iter >= 1, bins <= 1024, else CT_E_BADARG; out_f64 / out_f32 / psnr_out off their element
+ * size: CT_E_ALIGN; ws missing, not 16-byte aligned or smaller than ct_idt_u8_workspace_bytes(batch, n_iter, bins, n_t,
+ * out_f64 == NULL): CT_E_WORKSPACE -- all before anything touches the device.  ct_idt_u8_workspace_bytes is 0 for refused
+ * arguments; state_in_ws adds exactly 24 * n_t * batch bytes rounded up to 16.  Added under ABI 9.                          */
+size_t ct_idt_u8_workspace_bytes(int batch, int n_iter, int bins, int64_t n_t, int state_in_ws);
+int ct_idt_u8(const uint8_t *target, int64_t n_t, const uint8_t *reference, int64_t n_r, const uint8_t *gt, int batch,
+              const double *rot, const double *rinv, int n_iter, int bins, int input_f32, int round_dr_f32,
+              double *out_f64, float *out_f32, uint8_t *out_u8, double *psnr_out,
+              void *ws, size_t ws_bytes, const ct_idt_debug *dbg, void *stream);
+
 /* ---- a5-a9: DCMCS3DI forward building blocks (methods/dcmcs3di.py:41-66, pasmnet/ *.py) ----
  * NCHW float32 tensors as the reference's modules exchange them; exact-f32 MFMA arithmetic.
  *
