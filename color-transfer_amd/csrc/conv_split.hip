@@ -649,8 +649,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                                         v.x *= q1.x; v.y *= q1.y; v.z *= q1.z; v.w *= q1.w;
                                     } else {
                                         const float4 q2 = *reinterpret_cast<const float4 *>(a.p2 + po);
-                                        v.x = (1.0f - q1.x) * q2.x + q1.x * v.x; v.y = (1.0f - q1.y) * q2.y + q1.y * v.y;
-                                        v.z = (1.0f - q1.z) * q2.z + q1.z * v.z; v.w = (1.0f - q1.w) * q2.w + q1.w * v.w;
+                                        v.x = gru_blend(q1.x, q2.x, v.x); v.y = gru_blend(q1.y, q2.y, v.y);
+                                        v.z = gru_blend(q1.z, q2.z, v.z); v.w = gru_blend(q1.w, q2.w, v.w);
                                     }
                                 }
                                 if (a.clamp) {

@@ -59,6 +59,11 @@ struct DynLdsAttr {
         if (e__ != hipSuccess) return (int)e__;     \
     } while (0)
 
+// The GRU blend (1 - z) h + z q (reg_refine.py:41-55) as two fused steps, (h - z h) + z q: two roundings, within 1.5 ulp of the
+// larger product of the exact value.  The plain float32 expression has four roundings (1 - z, both products, the sum) and reaches
+// 2.5 ulp; eltwise op 2 (gmflow.hip) and the convolution post-op 2 (conv_split.hip) both call this, so they agree bit for bit.
+__device__ __forceinline__ float gru_blend(float z, float h, float q) { return fmaf(z, q, fmaf(-z, h, h)); }
+
 __device__ __forceinline__ int reflect(int i, int n) {     // torch "reflect" padding (no edge repeat); n >= 6 here
     i = i < 0 ? -i : i;
     return i >= n ? 2 * (n - 1) - i : i;

@@ -7,6 +7,10 @@
 
 namespace ct {
 
+// ReLU that propagates NaN like torch.relu / F.relu (`v > 0 ? v : 0` turns a NaN into 0 and hides it from every isfinite check
+// downstream); every other input, -0 included, gives what that form gives
+__device__ __forceinline__ float relu_nan(float v) { return v <= 0.f ? 0.f : v; }
+
 // =================================================================================================
 // InstanceNorm2d (affine=False, biased variance, eps): one workgroup per (n, c) plane, two passes.
 //   mode 0: y = IN(x)          mode 1: y = relu(IN(x))          mode 2: y = relu(skip + relu(IN(x)))   (backbone.py:34-39)
@@ -37,8 +41,8 @@ __global__ __launch_bounds__(256) void inorm_kernel(const float *__restrict__ x,
     const float fm = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)eps));
     for (int i = threadIdx.x; i < plane; i += 256) {
         float v = (x[base + i] - fm) * rstd;
-        if (mode >= 1) v = v > 0.f ? v : 0.f;
-        if (mode == 2) { v += skip[base + i]; v = v > 0.f ? v : 0.f; }
+        if (mode >= 1) v = relu_nan(v);
+        if (mode == 2) { v += skip[base + i]; v = relu_nan(v); }
         y[base + i] = v;
     }
 }
@@ -90,15 +94,15 @@ __global__ __launch_bounds__(256) void inorm_apply_kernel(const float *__restric
     const size_t base = (size_t)blockIdx.x * plane;
     for (int i = i0 + threadIdx.x; i < i1; i += 256) {
         float v = (x[base + i] - fm) * rstd;
-        if (mode >= 1) v = v > 0.f ? v : 0.f;
-        if (mode == 2) { v += skip[base + i]; v = v > 0.f ? v : 0.f; }
+        if (mode >= 1) v = relu_nan(v);
+        if (mode == 2) { v += skip[base + i]; v = relu_nan(v); }
         y[base + i] = v;
     }
 }
 
 // =================================================================================================
 // Elementwise helpers
-//   op 0: y = a + b              op 1: y = a * b                  op 2: y = (1 - z) * h + z * q   (a=z, b=h, c=q)
+//   op 0: y = a + b              op 1: y = a * b                  op 2: y = (1 - z) * h + z * q   (a=z, b=h, c=q; gru_blend)
 //   op 3: y = (a / 255 - mean[c]) / std[c]   (normalize_img, utils.py:26-34; a: [N,3,H,W], plane given)
 //   op 4: y = a * s0             op 5: tanh(a) for channels < split, relu(a) otherwise (refine_proj chunk, unimatch.py:320-323)
 // =================================================================================================
@@ -110,7 +114,7 @@ __global__ void eltwise_kernel(const float *__restrict__ a, const float *__restr
     switch (op) {
         case 0: v = a[i] + b[i]; break;
         case 1: v = a[i] * b[i]; break;
-        case 2: v = (1.0f - a[i]) * b[i] + a[i] * c[i]; break;
+        case 2: v = gru_blend(a[i], b[i], c[i]); break;
         case 3: {
             const int ch = (int)((i / plane) % 3);
             const float mean = ch == 0 ? 0.485f : (ch == 1 ? 0.456f : 0.406f);
@@ -121,7 +125,7 @@ __global__ void eltwise_kernel(const float *__restrict__ a, const float *__restr
         case 4: v = a[i] * s0; break;
         default: {
             const int ch = (int)((i / plane) % chans);
-            v = ch < split ? tanhf(a[i]) : (a[i] > 0.f ? a[i] : 0.f);
+            v = ch < split ? tanhf(a[i]) : relu_nan(a[i]);
         }
     }
     y[i] = v;
@@ -150,6 +154,8 @@ __global__ void bilinear_resize_kernel(const float *__restrict__ in, float *__re
     out[i] = v * (((int)(nc % C) == 0) ? mul0 : mul1);
 }
 
+__device__ __forceinline__ float tap_index(float f) { return f < -2.f ? -2.f : (f > 2147483520.f ? 2147483520.f : f); }
+
 // geometry.py:43-75: out = grid_sample(img, (x + flow_x, y + flow_y)), bilinear, zeros padding, align_corners=True
 __global__ void flow_warp_kernel(const float *__restrict__ img, const float *__restrict__ flow, float *__restrict__ out, int N, int C,
                                  int H, int W) {
@@ -163,7 +169,10 @@ __global__ void flow_warp_kernel(const float *__restrict__ img, const float *__r
     const float gx = 2.0f * sx / (float)(W - 1) - 1.0f, gy = 2.0f * sy / (float)(H - 1) - 1.0f;
     const float px = ((gx + 1.0f) * 0.5f) * (float)(W - 1), py = ((gy + 1.0f) * 0.5f) * (float)(H - 1);
     const float x0f = floorf(px), y0f = floorf(py);
-    const int x0 = (int)x0f, y0 = (int)y0f;
+    // A finite flow beyond +-2^31 has no defined float -> int conversion, and on the saturated INT_MAX the guard of the right-hand
+    // tap, compiled as `x0 > -2 && wrapped(x0 + 1) < W`, is TRUE: a load 8 GB past the plane.  Any index outside [-1, W - 1] has no
+    // tap, so convert a clamped copy (the weights keep x0f): [-2, 2^31 - 128] converts exactly and x0 + 1 cannot overflow.
+    const int x0 = (int)tap_index(x0f), y0 = (int)tap_index(y0f);
     const float wx1 = px - x0f, wy1 = py - y0f, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
     const bool vx0 = x0 >= 0 && x0 < W, vx1 = x0 + 1 >= 0 && x0 + 1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y0 + 1 >= 0 && y0 + 1 < H;
     for (int c = 0; c < C; ++c) {
