@@ -9,7 +9,7 @@
 // at 5 TB/s).  So: no fp16 split, no scales, no LDS, no barrier.  A wave keeps the whole 64 x 64 weight matrix in 64 registers (one A
 // fragment per lane and 2-channel K step), walks 32-pixel row segments, fetches the segment's 64 channel values per pixel with 32
 // coalesced dword loads per lane a tile ahead, runs 64 MFMAs and stores 16 bytes per lane and 4 output channels.  Arithmetic: float32
-// products, float32 accumulation in the matrix pipe's order -- the "exact" class of cnn.hip, closer to the reference than the two-piece
+// products, float32 accumulation in the matrix pipe's order -- the "exact" class of conv_exact.hip, closer to the reference than the two-piece
 // form it replaces.
 #include "ct_common.h"
 #include "ct_split16.h"      // f32x16

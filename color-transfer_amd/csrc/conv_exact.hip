@@ -1,13 +1,10 @@
-// cnn.hip -- DCMCS3DI forward building blocks on gfx950 (MI355X), exact-float32 MFMA.
+// conv_exact.hip -- the exact-float32 tile convolution on gfx950 (MI355X): v_mfma_f32_32x32x2_f32.
 //
 // Replaces the ATen op sequences of the reference's CNN path:
 //   B1/B2/B3/B5  Conv2d 3x3 / 1x1 (+bias, +LeakyReLU(0.01), +residual, +clamp)
 //                methods/dcmcs3di.py:41-51, pasmnet/backbone.py:8-15, pasmnet/attention.py:13-16
 //                -> conv_mfma_kernel<KS, MT>  (implicit GEMM, LDS-tiled, v_mfma_f32_32x32x2_f32)
-//   B4           cost = Q.K/c, softmax, warp(att @ V), valid mask (column sums > 0.1)
-//                pasmnet/attention.py:39-46, pasmnet/utils.py:30-35,123-125, dcmcs3di.py:58,65
-//                -> pam_attend_kernel<MODE> (+ pam_valid_kernel): never writes a [H,W,W] tensor
-//                unless the caller asks for the attention maps.
+// (B4, the materialised parallax attention, is pam.hip.)
 //
 // Layout: NCHW float32, exactly what the reference's modules exchange (no layout change at the
 // boundary).  The GEMM is oriented M = output channels (weights are the A operand), N = 32
@@ -20,6 +17,7 @@
 #include "ct_common.h"
 #include "ct_conv.h"
 #include "ct_split.h"
+#include "ct_stamps.h"
 
 namespace ct {
 
@@ -152,15 +150,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, int tiles
     };
 
     if (n_stages == 0) return;
-#ifdef CT_CONV_PROFILE
-    // diagnostic build: per-phase cycle totals of wave 0 of each workgroup -> a.prof[block][8]
-    unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt0;
-#define CT_STAMP(var) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory")
-#define CT_PHASE(i) do { unsigned long long t__; CT_STAMP(t__); pt[i] += t__ - pt0; pt0 = t__; } while (0)
-    CT_STAMP(pt0);
-#else
-#define CT_PHASE(i) do { } while (0)
-#endif
+    CT_STAMPS_BEGIN(8);       // -DCT_STAMPS (ct_stamps.h, tools/prof_conv.py exact): phase totals of wave 0 of each workgroup
+    CT_STAMP0();
     f32x16 acc[RPW][MT];
     float wa[KSTEPS][MT], wb[KSTEPS][MT];
     // ---- phase stagger --------------------------------------------------------------------------------------
@@ -265,9 +256,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, int tiles
                     for (int r = 0; r < 16; ++r) acc[q][m][r] += bv[r];
             }
         }
-        CT_PHASE(0);                                       // store_tile + acc init of the previous iteration
+        CT_STAMP(0);                                       // store_tile + acc init of the previous iteration
         __syncthreads();                                   // this stage's tile is visible
-        CT_PHASE(1);
+        CT_STAMP(1);
         const bool next_stage = (stage + 1 < n_stages);
         const int next_chunk = (chunk + 1 == n_chunks) ? 0 : chunk + 1;
         const int next_grp = (next_chunk == 0) ? (int)((blockIdx.x + (k + 1) * gridDim.x) % a.groups) : grp;
@@ -317,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, int tiles
 #pragma unroll
                 for (int m = 0; m < MT; ++m) wa[p][m] = wb[p][m];
         }
-        CT_PHASE(2);                                       // tap loop (MFMAs + prefetch issue)
+        CT_STAMP(2);                                       // tap loop (MFMAs + prefetch issue)
         if (chunk + 1 == n_chunks) {
             // ---- epilogue: lane owns pixels (y0 + wave*RPW + q, x0+nl), channels (r&3)+8(r>>2)+4hl of each 32-tile ----
             const int t = (blockIdx.x + k * gridDim.x) / a.groups;
@@ -373,18 +364,13 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, int tiles
             }
             if (next_stage) init_acc(k + 1);   // the stores above are fire-and-forget; start the next tile's skip loads
         }
-        CT_PHASE(3);                       // epilogue
+        CT_STAMP(3);                       // epilogue
         __syncthreads();                   // every wave is done reading this stage's tile
-        CT_PHASE(4);
+        CT_STAMP(4);
         if (next_stage) store_tile();      // waits for the prefetched loads, then fills the tile
     }
-#ifdef CT_CONV_PROFILE
-    CT_PHASE(0);
-    if (tid == 0 && a.prof) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a.prof[(size_t)blockIdx.x * 8 + i] = pt[i];
-    }
-#endif
+    CT_STAMP(0);
+    if (wave == 0) CT_STAMPS_WRITE(a.prof, 1, 0, 8);
 }
 
 template <int KH, int KW, int MT, bool GEN>
@@ -399,8 +385,8 @@ int launch_conv(const ConvArgs &a, int N, hipStream_t s) {
     const long long n_tiles = (long long)tiles_x * tiles_y * N * a.groups;
     if (n_tiles > 0x7fffffffLL) return CT_E_BADARG;
     const int grid = n_tiles < 2 * kNumCUs ? (int)n_tiles : 2 * kNumCUs;   // persistent: two workgroups per CU
-    if (vec) hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, MT, true, GEN>), dim3(grid), dim3(256), lds, s, a, tiles_x, tiles_y, (int)n_tiles);
-    else hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, MT, false, GEN>), dim3(grid), dim3(256), lds, s, a, tiles_x, tiles_y, (int)n_tiles);
+    if (vec) hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, MT, true, GEN>), dim3(grid), dim3(256), lds, s, CT_STAMPS_ARGS(a), tiles_x, tiles_y, (int)n_tiles);
+    else hipLaunchKernelGGL((conv_mfma_kernel<KH, KW, MT, false, GEN>), dim3(grid), dim3(256), lds, s, CT_STAMPS_ARGS(a), tiles_x, tiles_y, (int)n_tiles);
     CT_CHECK_LAUNCH();
     return CT_OK;
 }
@@ -415,258 +401,6 @@ int conv_fast(const ConvArgs &a, int N, int kh, int kw, hipStream_t s) {
     return 1;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Parallax attention for one direction (pasmnet/attention.py:39-46 + utils.py:30-35,123-125).
-//   S[i][j] = (1/C) sum_c Q[c][h][i] K[c][h][j] ; P = softmax_j S
-//   MODE 0 (attend): out[c][h][i] = sum_j P[i][j] V[c][h][j] for the CV channels of `v` and the 3 of `rgb`
-//   MODE 1 (colsum): colpart[h][tile][j] = sum_{i in tile} P[i][j]      (valid mask numerator)
-//   optional att[h][i][j] = P (the API's attention map), written only when the pointer is non-null
-// grid = (ceil(W/32), H, N), block 256, dynamic LDS = 32*(W+1) floats + V staging
-// ---------------------------------------------------------------------------------------------
-struct PamArgs {
-    const float *q, *k;        // [N][C][H][W]
-    const float *v;            // [N][CV][H][W]      (MODE 0)
-    const float *rgb;          // [N][3][H][W]       (MODE 0)
-    float *out_v, *out_rgb;    // [N][CV][H][W], [N][3][H][W]
-    float *colpart;            // [N][H][tiles][W]   (MODE 1)
-    float *att;                // nullable [N][H][W][W]
-    int C, CV, H, W;
-};
-
-constexpr int kPamKC = 128;  // keys staged per S step (one 32-key MFMA tile per wave)
-constexpr int kPamJC = 64;   // keys staged per PV step
-constexpr int kPamC = 64;    // channels of q/k (DCMCS3DI: channels = 64)
-
-// Cooperative copy of rows [r][j0 .. j0+NCOLS) of a row-major [rows][plane-strided] slab into registers
-// (NV4 float4 per thread), 16-byte loads when the row base is aligned, zero fill outside [0,W) x [0,rows).
-template <int NROWS, int NCOLS>
-struct RowChunk {
-    static constexpr int V4_PER_ROW = NCOLS / 4;
-    static constexpr int NV4 = (NROWS * V4_PER_ROW + 255) / 256;
-    float4 v[NV4];
-    // src(r) = row pointer of row r at column 0, or nullptr for a zero row
-    template <typename RowPtr>
-    __device__ __forceinline__ void fetch(RowPtr src, int j0, int W, bool vec, int tid) {
-#pragma unroll
-        for (int i = 0; i < NV4; ++i) {
-            int f = tid + i * 256;
-            asm volatile("" : "+v"(f));
-            const int r = f / V4_PER_ROW, g = f - r * V4_PER_ROW;
-            const int j = j0 + 4 * g;
-            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float *p = (r < NROWS) ? src(r) : nullptr;
-            if (p && j < W) {
-                if (vec) x = *reinterpret_cast<const float4 *>(p + j);
-                else {
-                    x.x = p[j];
-                    if (j + 1 < W) x.y = p[j + 1];
-                    if (j + 2 < W) x.z = p[j + 2];
-                    if (j + 3 < W) x.w = p[j + 3];
-                }
-            }
-            v[i] = x;
-        }
-    }
-    // LDS image [NROWS][LD]; LD % 4 == 0 -> one 16-byte store, else four scalar stores
-    template <int LD>
-    __device__ __forceinline__ void store(float *lds, int tid) const {
-#pragma unroll
-        for (int i = 0; i < NV4; ++i) {
-            const int f = tid + i * 256;
-            const int r = f / V4_PER_ROW, g = f - r * V4_PER_ROW;
-            if (r < NROWS) {
-                float *d = lds + r * LD + 4 * g;
-                if (LD % 4 == 0) *reinterpret_cast<float4 *>(d) = v[i];
-                else { d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w; }
-            }
-        }
-    }
-};
-
-// TQ = queries per workgroup: 32, or 16 for wide images (one TQ x W tile of S must fit the 160 KiB LDS; the MFMA
-// tile stays 32 x 32 with the upper 16 query rows idle)
-template <int MODE, int TQ>
-__global__ __launch_bounds__(256) void pam_attend_kernel(PamArgs a) {
-    extern __shared__ float smem[];
-    const int W = a.W, SW = W | 1;                 // odd row stride: column reads are conflict free
-    constexpr int VST = kPamJC + 1;                // odd: the PV A-operand reads walk down a column
-    float *S = smem;                               // [TQ][SW]
-    float *Qs = smem + TQ * SW;                    // [64][TQ]
-    float *Ks = Qs + kPamC * TQ;               // [64][128]   (S phase)  /  Vs [96][65] (PV phase), aliased
-    float *Vs = Ks;
-    const int i0 = blockIdx.x * TQ, h = blockIdx.y, n = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nl = lane & 31, hl = lane >> 5;
-    const size_t plane = (size_t)a.H * W;
-    const float *q = a.q + (size_t)n * kPamC * plane + (size_t)h * W;
-    const float *k = a.k + (size_t)n * kPamC * plane + (size_t)h * W;
-    const float inv_c = 1.0f / (float)kPamC;
-    const bool vec = (W % 4 == 0) && (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0);
-
-    // ---- S tile = Q^T K / C : M = query i (A = Q[c][i]), N = key j (B = K[c][j]), K = channels ----
-    {
-        RowChunk<kPamC, TQ> qc;
-        qc.fetch([&](int r) { return q + (size_t)r * plane; }, i0, W, vec, tid);
-        RowChunk<kPamC, kPamKC> kc;
-        kc.fetch([&](int r) { return k + (size_t)r * plane; }, 0, W, vec, tid);
-        qc.template store<TQ>(Qs, tid);
-        kc.template store<kPamKC>(Ks, tid);
-        __syncthreads();
-        float qa[kPamC / 2];                        // this lane's A operands for all 32 k-steps
-#pragma unroll
-        for (int p = 0; p < kPamC / 2; ++p) qa[p] = (nl < TQ) ? Qs[(2 * p + hl) * TQ + nl] : 0.f;
-        for (int j0 = 0; j0 < W; j0 += kPamKC) {
-            const bool more = (j0 + kPamKC < W);
-            if (more) kc.fetch([&](int r) { return k + (size_t)r * plane; }, j0 + kPamKC, W, vec, tid);   // next chunk in flight
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            const float *brow = Ks + hl * kPamKC + wave * 32 + nl;
-#pragma unroll
-            for (int p = 0; p < kPamC / 2; ++p) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(qa[p], brow[p * 2 * kPamKC], acc, 0, 0, 0);
-            // D[i][j]: lane holds key column j, query rows (r&3)+8(r>>2)+4hl
-            const int kj = j0 + wave * 32 + nl;
-            if (kj < W) {
-#pragma unroll
-                for (int r = 0; r < TQ / 2; ++r) S[((r & 3) + 8 * (r >> 2) + 4 * hl) * SW + kj] = acc[r] * inv_c;   // rows < TQ
-            }
-            __syncthreads();                        // everyone is done with this K chunk
-            if (more) {
-                kc.template store<kPamKC>(Ks, tid);
-                __syncthreads();
-            }
-        }
-    }
-    // prefetch the first V chunk while the softmax runs (MODE 0)
-    const int CT = a.CV + 3;                        // feature channels + the 3 RGB channels of `right`
-    const float *v = MODE == 0 ? a.v + (size_t)n * a.CV * plane + (size_t)h * W : nullptr;
-    const float *rgb = MODE == 0 ? a.rgb + (size_t)n * 3 * plane + (size_t)h * W : nullptr;
-    const bool vecv = MODE == 0 && (W % 4 == 0) &&
-                      (((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(rgb)) & 15) == 0);
-    auto vrow = [&](int r) -> const float * {
-        return r < a.CV ? v + (size_t)r * plane : (r < CT ? rgb + (size_t)(r - a.CV) * plane : nullptr);
-    };
-    RowChunk<96, kPamJC> vc;
-    if (MODE == 0) vc.fetch(vrow, 0, W, vecv, tid);
-
-    // ---- row softmax (F.softmax(dim=-1)): 8 rows per wave ----
-    for (int rr = 0; rr < TQ / 4; ++rr) {
-        const int row = wave * (TQ / 4) + rr;
-        float *srow = S + row * SW;
-        float mx = -INFINITY;
-        for (int j = lane; j < W; j += 64) mx = fmaxf(mx, srow[j]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        float sum = 0.f;
-        for (int j = lane; j < W; j += 64) {
-            const float e = expf(srow[j] - mx);
-            srow[j] = e;
-            sum += e;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-        const float inv = 1.0f / sum;
-        const bool live = (i0 + row) < W;
-        for (int j = lane; j < W; j += 64) {
-            const float p = live ? srow[j] * inv : 0.f;
-            srow[j] = p;
-            if (a.att && live) a.att[(((size_t)n * a.H + h) * W + (i0 + row)) * W + j] = p;
-        }
-    }
-    __syncthreads();
-    if (MODE == 1) {
-        // column sums over this tile's (live) query rows, fixed order
-        float *dst = a.colpart + (((size_t)n * a.H + h) * gridDim.x + blockIdx.x) * W;
-        for (int j = tid; j < W; j += 256) {
-            float s = 0.f;
-#pragma unroll
-            for (int r = 0; r < TQ; ++r) s += S[r * SW + j];
-            dst[j] = s;
-        }
-        return;
-    }
-    // ---- out[c][i] = sum_j V[c][j] P[i][j] : M = channel (A = V, staged [c][JC+1]), N = query (B = P) ----
-    const int mt_total = (CT + 31) / 32;            // 3 for CV = 64
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    vc.template store<VST>(Vs, tid);
-    __syncthreads();
-    for (int j0 = 0; j0 < W; j0 += kPamJC) {
-        const bool more = (j0 + kPamJC < W);
-        if (more) vc.fetch(vrow, j0 + kPamJC, W, vecv, tid);     // next chunk in flight under the MFMAs
-        if (wave < mt_total) {
-            const float *arow = Vs + (wave * 32 + nl) * VST + hl;
-            const float *brow = S + (nl < TQ ? nl : 0) * SW + j0 + hl;
-#pragma unroll
-            for (int jj = 0; jj < kPamJC; jj += 2) {
-                const float bv = (nl < TQ && j0 + jj + hl < W) ? brow[jj] : 0.f;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[jj], bv, acc, 0, 0, 0);
-            }
-        }
-        __syncthreads();
-        if (more) {
-            vc.template store<VST>(Vs, tid);
-            __syncthreads();
-        }
-    }
-    if (wave < mt_total) {
-        const int x = i0 + nl;
-        if (nl < TQ && x < W) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-                if (c < a.CV) a.out_v[((size_t)n * a.CV + c) * plane + (size_t)h * W + x] = acc[r];
-                else if (c < CT) a.out_rgb[((size_t)n * 3 + (c - a.CV)) * plane + (size_t)h * W + x] = acc[r];
-            }
-        }
-    }
-}
-
-// valid[n][0][h][j] = (sum over query tiles of colpart) > 0.1, as 0.0 / 1.0 (bool -> float promotion of
-// torch.cat, dcmcs3di.py:59); colsum (pre-threshold) is also written for the parity tests.
-__global__ void pam_valid_kernel(const float *__restrict__ colpart, int tiles, int H, int W, float *__restrict__ valid,
-                                 float *__restrict__ colsum) {
-    const int n = blockIdx.z, h = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= W) return;
-    const float *p = colpart + (((size_t)n * H + h) * tiles) * W + j;
-    float s = 0.f;
-    for (int t = 0; t < tiles; ++t) s += p[(size_t)t * W];
-    const size_t o = ((size_t)n * H + h) * W + j;
-    valid[o] = s > 0.1f ? 1.0f : 0.0f;
-    if (colsum) colsum[o] = s;
-}
-
-template <int MODE, int TQ>
-static int launch_pam_tq(const PamArgs &a, int N, hipStream_t s, size_t lds) {
-    static DynLdsAttr attr;             // per instantiation, per device
-    {
-        hipError_t e = attr.ensure(reinterpret_cast<const void *>(&pam_attend_kernel<MODE, TQ>), lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dim3 grid((a.W + TQ - 1) / TQ, a.H, N);
-    hipLaunchKernelGGL((pam_attend_kernel<MODE, TQ>), grid, dim3(256), lds, s, a);
-    CT_CHECK_LAUNCH();
-    return CT_OK;
-}
-
-static int pam_tq(int W) {   // queries per workgroup such that S (TQ x W) + Q tile + K chunk fit the 160 KiB LDS
-    const size_t lds32 = ((size_t)32 * (W | 1) + kPamC * 32 + kPamC * kPamKC) * sizeof(float);
-    const size_t lds16 = ((size_t)16 * (W | 1) + kPamC * 16 + kPamC * kPamKC) * sizeof(float);
-    if (lds32 <= 160 * 1024) return 32;
-    if (lds16 <= 160 * 1024) return 16;
-    return 0;
-}
-
-template <int MODE>
-static int launch_pam(const PamArgs &a, int N, hipStream_t s) {
-    static_assert(96 * (kPamJC + 1) <= kPamC * kPamKC, "V chunk must fit the K chunk region");
-    if (a.C != kPamC) return CT_E_BADARG;
-    const int tq = pam_tq(a.W);
-    if (tq == 0) return CT_E_BADARG;   // W > 1982: needs the streaming (online-softmax) variant
-    const size_t lds = ((size_t)tq * (a.W | 1) + kPamC * tq + kPamC * kPamKC) * sizeof(float);
-    return tq == 32 ? launch_pam_tq<MODE, 32>(a, N, s, lds) : launch_pam_tq<MODE, 16>(a, N, s, lds);
-}
-
 }  // namespace ct
 
 extern "C" {
@@ -677,64 +411,11 @@ int ct_conv2d_f32(const float *in, const float *wp, const float *bias, const flo
     if (!in || !wp || !bias || !out || n < 0 || cin < 1 || cout < 1 || cout > 64 || h < 0 || w < 0) return CT_E_BADARG;
     if ((ksize != 1 && ksize != 3) || (act != 0 && act != 1)) return CT_E_BADARG;
     if (n == 0 || h == 0 || w == 0) return CT_OK;
-    ct::ConvArgs a;
-    a.in = in; a.in2 = nullptr; a.cin1 = cin; a.in2_bstride = 0; a.wp = wp; a.bias = bias; a.residual = residual; a.out = out;
-    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
-    a.in_bstride = in_bstride; a.out_bstride = out_bstride; a.res_bstride = res_bstride;
-    a.act = act; a.clamp = clamp; a.groups = 1; a.prof = nullptr;
+    const ct::ConvArgs a = ct::conv_args(in, wp, bias, residual, out, cin, cout, h, w, in_bstride, out_bstride, res_bstride, act, clamp, 1);
     hipStream_t s = (hipStream_t)stream;
     const int mt = cout > 32 ? 2 : 1;
     if (ksize == 3) return mt == 2 ? ct::launch_conv<3, 3, 2, false>(a, n, s) : ct::launch_conv<3, 3, 1, false>(a, n, s);
     return mt == 2 ? ct::launch_conv<1, 1, 2, false>(a, n, s) : ct::launch_conv<1, 1, 1, false>(a, n, s);
-}
-
-#ifdef CT_CONV_PROFILE
-// diagnostic build only (tools/prof_conv.py): 3x3 64->64 conv with per-phase cycle stamps, prof[grid][8]
-int ct_conv2d_prof_f32(const float *in, const float *wp, const float *bias, const float *residual, float *out, int n,
-                       int cin, int cout, int h, int w, unsigned long long *prof, void *stream) {
-    ct::ConvArgs a;
-    a.in = in; a.in2 = nullptr; a.cin1 = cin; a.in2_bstride = 0; a.wp = wp; a.bias = bias; a.residual = residual; a.out = out;
-    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
-    a.in_bstride = (long long)cin * h * w; a.out_bstride = (long long)cout * h * w; a.res_bstride = a.out_bstride;
-    a.act = 0; a.clamp = 0; a.groups = 1; a.prof = prof;
-    return ct::launch_conv<3, 3, 2, false>(a, n, (hipStream_t)stream);
-}
-#endif
-
-size_t ct_pam_workspace_bytes(int n, int h, int w) {
-    if (n < 0 || h < 0 || w < 0) return 0;
-    const int tq = ct::pam_tq(w);
-    if (tq == 0) return 0;
-    return (size_t)n * h * ((w + tq - 1) / tq) * w * sizeof(float);
-}
-
-int ct_pam_attend_f32(const float *q, const float *k, const float *v, const float *rgb, float *out_v, float *out_rgb,
-                      float *att, int n, int c, int cv, int h, int w, void *stream) {
-    if (!q || !k || !v || !rgb || !out_v || !out_rgb || n < 0 || c < 1 || cv < 1 || cv > 93 || h < 0 || w < 0)
-        return CT_E_BADARG;
-    if (n == 0 || h == 0 || w == 0) return CT_OK;
-    ct::PamArgs a;
-    a.q = q; a.k = k; a.v = v; a.rgb = rgb; a.out_v = out_v; a.out_rgb = out_rgb; a.colpart = nullptr; a.att = att;
-    a.C = c; a.CV = cv; a.H = h; a.W = w;
-    return ct::launch_pam<0>(a, n, (hipStream_t)stream);
-}
-
-int ct_pam_valid_f32(const float *q, const float *k, float *valid, float *colsum, float *att, int n, int c, int h, int w,
-                     void *ws, size_t ws_bytes, void *stream) {
-    if (!q || !k || !valid || n < 0 || c < 1 || h < 0 || w < 0) return CT_E_BADARG;
-    if (n == 0 || h == 0 || w == 0) return CT_OK;
-    if (!ws || ws_bytes < ct_pam_workspace_bytes(n, h, w)) return CT_E_WORKSPACE;
-    ct::PamArgs a;
-    a.q = q; a.k = k; a.v = nullptr; a.rgb = nullptr; a.out_v = nullptr; a.out_rgb = nullptr;
-    a.colpart = reinterpret_cast<float *>(ws); a.att = att;
-    a.C = c; a.CV = 0; a.H = h; a.W = w;
-    int rc = ct::launch_pam<1>(a, n, (hipStream_t)stream);
-    if (rc) return rc;
-    const int tiles = (w + ct::pam_tq(w) - 1) / ct::pam_tq(w);
-    hipLaunchKernelGGL(ct::pam_valid_kernel, dim3((w + 255) / 256, h, n), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)ws, tiles, h, w, valid, colsum);
-    CT_CHECK_LAUNCH();
-    return CT_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // conv_generic.hip -- the GMFlow matcher's Conv2d for any kernel / stride / channel count (backbone.py, reg_refine.py),
 // NCHW float32 on the exact-f32 MFMA, and the space-to-depth pass that turns a stride-2 3x3 into a stride-1 2x2 for
-// conv_split.hip.  ct_gconv2d_f32 tries conv_direct.hip and cnn.hip's LDS-tiled kernels first (same packed weights).
+// conv_split.hip.  ct_gconv2d_f32 tries conv_direct.hip and conv_exact.hip's LDS-tiled kernels first (same packed weights).
 #include "ct_common.h"
 #include "ct_conv.h"
 #include "ct_split.h"
@@ -116,12 +116,8 @@ int ct_gconv2d_f32(const float *in, const float *wp, const float *bias, float *o
         if (rc != 1) return rc;
     }
     if (stride == 1 && pad_h == kh / 2 && pad_w == kw / 2 && (kh & 1) && (kw & 1) && bias) {
-        // stride-1 "same" convolution: the LDS-tiled persistent kernel of cnn.hip (same weight layout)
-        ct::ConvArgs f;
-        f.in = in; f.in2 = nullptr; f.cin1 = cin; f.in2_bstride = 0; f.wp = wp; f.bias = bias; f.residual = nullptr; f.out = out;
-        f.cin = cin; f.cout = cout; f.H = h; f.W = w;
-        f.in_bstride = in_bstride; f.out_bstride = out_bstride; f.res_bstride = 0;
-        f.act = act; f.clamp = 0; f.groups = a.coutp / 64; f.prof = nullptr;
+        // stride-1 "same" convolution: the LDS-tiled persistent kernel of conv_exact.hip (same weight layout)
+        const ct::ConvArgs f = ct::conv_args(in, wp, bias, nullptr, out, cin, cout, h, w, in_bstride, out_bstride, 0, act, 0, a.coutp / 64);
         const int rc = ct::conv_fast(f, n, kh, kw, (hipStream_t)stream);
         if (rc != 1) return rc;
     }

@@ -1,6 +1,6 @@
-// conv_split.hip -- the stride-1 convolutions of cnn.hip on the bf16 matrix pipe with float32-grade accuracy.
+// conv_split.hip -- the stride-1 convolutions of conv_exact.hip on the bf16 matrix pipe with float32-grade accuracy.
 //
-// v_mfma_f32_32x32x2_f32 (cnn.hip) runs at 1/16 of the bf16 MFMA rate on gfx950.  Here every float32 operand is split
+// v_mfma_f32_32x32x2_f32 (conv_exact.hip) runs at 1/16 of the bf16 MFMA rate on gfx950.  Here every float32 operand is split
 // into three bf16 pieces, x = hi + mid + lo (8 + 8 + 8 mantissa bits, each difference exact in float32), and a product
 // is evaluated as the six partial products whose weight is >= 2^-16 of the leading one
 //     a*b ~= a_lo*b_hi + a_hi*b_lo + a_mid*b_mid + a_mid*b_hi + a_hi*b_mid + a_hi*b_hi        (float32 accumulation)
@@ -14,10 +14,11 @@
 // is staged: a thread fetches 8 channels x 4 pixels with 16-byte loads, converts in registers and writes the LDS tile
 // [piece][row][k-half][column][8 channels] so that an MFMA B fragment (8 consecutive channels of one pixel) is one
 // conflict-free 16-byte read.  Epilogue (bias, activation, ResB skip, clamp, 16-byte stores through a per-wave LDS
-// transpose) as in cnn.hip.  Requires W % 4 == 0 and 16-byte aligned tensors; other cases stay on the f32 kernel.
+// transpose) as in conv_exact.hip.  Requires W % 4 == 0 and 16-byte aligned tensors; other cases stay on the f32 kernel.
 #include "ct_common.h"
 #include "ct_conv.h"
 #include "ct_split.h"
+#include "ct_stamps.h"
 
 namespace ct {
 
@@ -199,14 +200,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                         sp16_split2x2(x0 * sc, x1 * sc, hw[jp], lw[jp]);
                         continue;
                     }
-#ifdef CT_SPLIT_SCALAR
-                    unsigned int h0, m0, l0, h1, m1, l1;
-                    split3(x0, h0, m0, l0);
-                    split3(x1, h1, m1, l1);
-                    hw[jp] = h0 | (h1 << 16); mw[jp] = m0 | (m1 << 16); lw[jp] = l0 | (l1 << 16);
-#else
                     split3x2(x0, x1, hw[jp], mw[jp], lw[jp]);
-#endif
                 }
                 dst[px] = make_uint4(hw[0], hw[1], hw[2], hw[3]);
                 if constexpr (F16) {
@@ -261,15 +255,9 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
     };
     unsigned long long w_off = w_unit_off(wcur);
     const char *wlane = reinterpret_cast<const char *>(a.wp) + lane * 16;
-#ifdef CT_SPLIT_ABL_NOW
-    int wi_n = 0;
-#endif
     auto w_issue = [&]() {                                 // the loader wave only
         const char *src = wlane + w_off;
         const unsigned int dst = wl_addr + (unsigned int)(wi_slot * WSLOT * 16);   // + 16 * lane is implied by the instruction
-#ifdef CT_SPLIT_ABL_NOW
-        if (wi_n++ < TAPS)                                 // diagnostic: only the first stage's weights are ever loaded
-#endif
 #pragma unroll
         for (int f = 0; f < NP * MT; ++f) glds16(src + f * 1024, __builtin_amdgcn_readfirstlane(dst + f * 1024));
         w_off += NP * MT * 1024;
@@ -306,15 +294,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
 #undef CT_VMCNT
     };
 
-#ifdef CT_CONV_PROFILE
-    // diagnostic build (make prof, tools/prof_conv_split.py): per-phase cycle totals of every wave 0 -> a.prof[block][8]
-    unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt0;
-#define CT_STAMP(var) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory")
-#define CT_PHASE(i) do { unsigned long long t__; CT_STAMP(t__); pt[i] += t__ - pt0; pt0 = t__; } while (0)
-    CT_STAMP(pt0);
-#else
-#define CT_PHASE(i) do { } while (0)
-#endif
+    CT_STAMPS_BEGIN(8);       // -DCT_STAMPS (ct_stamps.h, tools/prof_conv.py split): phase totals of waves 0 and 3 (the weight streamer)
+    CT_STAMP0();
     f32x16 acc[RPW][MT];
     // phase stagger of the two co-resident workgroups (see conv_mfma_kernel)
     if (n_stages >= 2 * n_chunks) {
@@ -435,9 +416,9 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
                     for (int r = 0; r < 16; ++r) acc[q][m][r] += bv[r];
             }
         }
-        CT_PHASE(0);                                       // store_tile / accumulator init
+        CT_STAMP(0);                                       // store_tile / accumulator init
         __syncthreads();                                   // this stage's tile is visible
-        CT_PHASE(1);
+        CT_STAMP(1);
         const bool next_stage = (stage + 1 < n_stages);
         // B fragments of tap t: [q][piece]; read one tap ahead of the MFMAs that consume them
         uint4 bc[RPW][NP], bn[RPW][NP];
@@ -506,10 +487,10 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
             for (int q = 0; q < RPW; ++q)
 #pragma unroll
                 for (int p = 0; p < NP; ++p) bc[q][p] = bn[q][p];
-            CT_PHASE(2);                                     // tap work: LDS operand reads + MFMAs (+ prefetch issue)
-            if (wloader) { w_landed(g); CT_PHASE(6); }
+            CT_STAMP(2);                                     // tap work: LDS operand reads + MFMAs (+ prefetch issue)
+            if (wloader) { w_landed(g); CT_STAMP(6); }
             if (!last_tap) __syncthreads();                  // weight slot g%4 is free, slot (g+1)%4 is published
-            CT_PHASE(5);
+            CT_STAMP(5);
         }
         if (F16 && seg_last && seg_k == 1) {
             // ---- stream-K hand-off: the head piece's partial sums, unscaled, [(q, m, r / 2)][thread] float2 into this workgroup's
@@ -732,9 +713,9 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
             }
         }
         if constexpr (F16) { if (next_stage) note_max(); }   // waits for the tile loads issued at tap 0
-        CT_PHASE(3);                       // epilogue
+        CT_STAMP(3);                       // epilogue
         __syncthreads();                   // every wave is done reading this stage's tile (F16: the next tile's maxima are visible)
-        CT_PHASE(4);
+        CT_STAMP(4);
         if constexpr (F16) {
             if (next_stage) {
                 const int et = tile_exp();
@@ -745,13 +726,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a, int tile
             if (next_stage) store_tile(1.f);
         }
     }
-#ifdef CT_CONV_PROFILE
-    CT_PHASE(0);
-    if (lane == 0 && (wave == 0 || wave == 3) && a.prof) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a.prof[((size_t)(wave ? 512 : 0) + blockIdx.x) * 8 + i] = pt[i];
-    }
-#endif
+    CT_STAMP(0);
+    if (wave == 0 || wave == 3) CT_STAMPS_WRITE(a.prof, 2, wave ? 1 : 0, 8);
 }
 
 // stream-K scratch: flags (one 32-bit word per workgroup, 4 KiB reserved), then one partial tile (256 threads x 64 floats) per workgroup
@@ -784,7 +760,7 @@ static int launch_split(const ConvArgs &a_in, int N, hipStream_t s) {
         if (e == 0u) e = epoch.fetch_add(1, std::memory_order_relaxed) + 1u;
         a.sk_epoch = e;
     }
-    hipLaunchKernelGGL((conv_split_kernel<KH, KW, GEN, F16>), dim3(grid), dim3(256), lds, s, a, tiles_x, tiles_y, (int)n_tiles);
+    hipLaunchKernelGGL((conv_split_kernel<KH, KW, GEN, F16>), dim3(grid), dim3(256), lds, s, CT_STAMPS_ARGS(a), tiles_x, tiles_y, (int)n_tiles);
     CT_CHECK_LAUNCH();
     return CT_OK;
 }
@@ -853,13 +829,9 @@ int ct_conv2d_split_f32(const float *in, const float *in2, int cin1, const float
     if (in3 && (!in2 || cin2 <= cin1 || cin2 >= cin || (cin2 % 16))) return CT_E_BADARG;
     if (scratch && ((reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < (long long)ct::kSkBytes)) return CT_E_WORKSPACE;
     if (n == 0 || h == 0 || w == 0) return CT_OK;
-    ct::ConvArgs a;
-    a.in = in; a.in2 = in2; a.cin1 = in2 ? cin1 : cin; a.in2_bstride = in2_bstride;
+    ct::ConvArgs a = ct::conv_args(in, wp_split, bias, residual, out, cin, cout, h, w, in_bstride, out_bstride, res_bstride, act, clamp, (cout + 63) / 64);
+    a.in2 = in2; a.cin1 = in2 ? cin1 : cin; a.in2_bstride = in2_bstride;
     a.in3 = in3; a.cin2 = in3 ? cin2 : cin; a.in3_bstride = in3_bstride;
-    a.wp = reinterpret_cast<const float *>(wp_split); a.bias = bias; a.residual = residual; a.out = out;
-    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
-    a.in_bstride = in_bstride; a.out_bstride = out_bstride; a.res_bstride = res_bstride;
-    a.act = act; a.clamp = clamp; a.groups = (cout + 63) / 64; a.prof = nullptr;
     a.res_pre = (residual && res_pre_act) ? 1 : 0;
     a.f16 = f16 ? 1 : 0; a.w_exp = f16 ? w_exp : 0;
     a.post_op = post_op; a.p1 = p1; a.p2 = p2;
@@ -877,30 +849,11 @@ int ct_conv2d_split_rows_f32(const float *in, const void *wp_split, const float 
     if (!in || !wp_split || !bias || !out_rows || n < 0 || cin < 1 || cout < 1 || h < 0 || w < 0 || act < 0 || act > 5) return CT_E_BADARG;
     if (rows_channels < 4 || rows_c0 < 0) return CT_E_BADARG;
     if (n == 0 || h == 0 || w == 0) return CT_OK;
-    ct::ConvArgs a;
-    a.in = in; a.in2 = nullptr; a.cin1 = cin; a.in2_bstride = 0;
-    a.wp = reinterpret_cast<const float *>(wp_split); a.bias = bias; a.residual = nullptr; a.out = out_rows;
-    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
-    a.in_bstride = in_bstride; a.out_bstride = 0; a.res_bstride = 0;
-    a.act = act; a.clamp = 0; a.groups = (cout + 63) / 64; a.prof = nullptr;
+    ct::ConvArgs a = ct::conv_args(in, wp_split, bias, nullptr, out_rows, cin, cout, h, w, in_bstride, 0, 0, act, 0, (cout + 63) / 64);
     a.rows_channels = rows_channels; a.rows_c0 = rows_c0;
     a.f16 = f16 ? 1 : 0; a.w_exp = f16 ? w_exp : 0;
     const int rc = ct::conv_split(a, n, kh, kw, true, (hipStream_t)stream);
     return rc == 1 ? CT_E_BADARG : rc;
 }
-
-#ifdef CT_CONV_PROFILE
-int ct_conv2d_split_prof_f32(const float *in, const void *wp_split, const float *bias, const float *residual, float *out, int n,
-                             int cin, int cout, int h, int w, unsigned long long *prof, int f16, int w_exp, int kh, int kw, void *stream) {
-    ct::ConvArgs a;
-    a.in = in; a.in2 = nullptr; a.cin1 = cin; a.in2_bstride = 0;
-    a.wp = reinterpret_cast<const float *>(wp_split); a.bias = bias; a.residual = residual; a.out = out;
-    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
-    a.in_bstride = (long long)cin * h * w; a.out_bstride = (long long)cout * h * w; a.res_bstride = a.out_bstride;
-    a.act = 0; a.clamp = 0; a.groups = (cout + 63) / 64; a.prof = prof;
-    a.f16 = f16; a.w_exp = w_exp;
-    return ct::conv_split(a, n, kh, kw, f16 != 0, (hipStream_t)stream);
-}
-#endif
 
 }  // extern "C"

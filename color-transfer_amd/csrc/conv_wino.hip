@@ -20,18 +20,18 @@
 // Rounding: float32 sums per position in a fixed order; results are float32-grade, not bitwise those of conv_ws.
 #include "ct_common.h"
 #include "ct_conv.h"
+#include "ct_row_segments.h"
 #include "ct_split.h"
+#include "ct_stamps.h"
 #include <type_traits>
 
 namespace ct {
 
 constexpr int kWnTiles = 16;           // 2x2 tiles per step = MFMA N: 32 output columns x 2 output rows
 constexpr int kWnTW = 2 * kWnTiles;    // output columns of a strip
-constexpr int kWnGroups = 10;          // staged input columns x0-4 .. x0+35 as aligned groups of four
 constexpr int kWnRowStride = 44;       // floats per channel row of the ring; index = column - (x0 - 4) + 1: tile t reads 2t + 4 .. 2t + 7 as two aligned
                                        // 8-byte words (16-byte aligned staging with 4-byte reads instead: 925 -> 1115 us)
 constexpr int kWnRing = 6;             // input rows resident: four in use, two being filled
-constexpr int kWnMStride = 17;         // floats per (position, cout) row of the M image (16 tiles + 1)
 constexpr int kWnThreads = 512;
 constexpr size_t kWnRingBytes = (size_t)kWnRing * 64 * kWnRowStride * sizeof(float);
 constexpr size_t kWnVBytes = (size_t)16 * 2 * 2 * 64 * 16;                       // [position][cin chunk][piece][lane] uint4
@@ -63,15 +63,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
     const int tt = tid & 15, cp = tid >> 4;          // T role: tile tt, channel pair cp
     const int dn = tid & 15, dc = tid >> 4;          // D role: tile dn, couts dc and dc + 32
 
-#ifdef CT_WN_PROFILE
-    // diagnostic build (tools/build_variant.sh, tools/prof_conv_wino.py): s_memtime ticks per phase and wave -> a.prof[block][wave][8]
-    unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt0;
-#define WN_STAMP0() asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pt0) :: "memory")
-#define WN_STAMP(i) do { unsigned long long t__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__) :: "memory"); pt[i] += t__ - pt0; pt0 = t__; } while (0)
-#else
-#define WN_STAMP0() do { } while (0)
-#define WN_STAMP(i) do { } while (0)
-#endif
+    CT_STAMPS_BEGIN(8);       // -DCT_STAMPS (ct_stamps.h, tools/prof_conv.py wino): s_memtime ticks per phase and wave
     uint4 wreg[2][4][2][2];              // [own position][cout block][cin chunk][piece]: A fragments
     int cur_grp = -1;
     const uint4 *wp16 = reinterpret_cast<const uint4 *>(a.wp);
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
         // one step; SB = (2 s) % 6 at compile time: the slot of row 2 s + i is (SB + i) % 6
         auto step = [&](int s, auto sb_c) {
             constexpr int SB = decltype(sb_c)::value;
-            WN_STAMP0();
+            CT_STAMP0();
             const int oy = y0 + 2 * s;
             // the tile row's scale: 2^ex * max |x| in [2^9, 2^10): |V| <= 4 max |x| stays below 2^12 like conv_ws's staged rows
             const float mx = fmaxf(__uint_as_float(rowmax[SB / 2]), __uint_as_float(rowmax[((SB + 2) % kWnRing) / 2]));
@@ -192,7 +184,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
             int ex = (fld == 0 || fld == 255) ? 0 : 136 - fld;
             ex = __builtin_amdgcn_readfirstlane(min(max(ex, -100), 100));
             const float scale = __uint_as_float((unsigned int)(127 + ex) << 23);
-            WN_STAMP(0);
+            CT_STAMP(0);
             // ---------------- T: (tile tt, channels 2 cp, 2 cp + 1) -> V -> fp16 pieces -> B image ----------------
             {
                 float v[2][4][4];
@@ -235,7 +227,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                     vb[p * (2 * 2 * 64 * 4) + 64 * 4] = lw[p];
                 }
             }
-            WN_STAMP(1);
+            CT_STAMP(1);
             // the skip rows of this step's outputs, requested after the transform (its live values and the 128 weight registers fill the file)
             float2 rq[2][2];
             if constexpr (HAS_RES) {
@@ -244,7 +236,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                 rq[1][0] = *reinterpret_cast<const float2 *>(rb + (rb1 + yy0)); rq[1][1] = *reinterpret_cast<const float2 *>(rb + (rb1 + yy1));
             }
             __syncthreads();
-            WN_STAMP(2);
+            CT_STAMP(2);
             // ---------------- C: fragments of the own positions, MFMAs, M image (in place of the fragments) ----------------
             {
                 // The matrix phase: six groups of eight independent MFMAs (one per accumulator); between the groups -- fenced, so that
@@ -261,7 +253,7 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                 for (int q = 0; q < 2; ++q)
 #pragma unroll
                     for (int pc = 0; pc < 2; ++pc) bq0[q][pc] = reinterpret_cast<const uint4 *>(vimg)[(((2 * wave + q) * 2 + 0) * 2 + pc) * 64 + lane];
-                WN_STAMP(3);
+                CT_STAMP(3);
                 auto group = [&](int kc, int pr, const uint4 (&bq)[2][2]) {      // small terms first: lo x hi, hi x lo, hi x hi
                     const int pw = pr == 0 ? 1 : 0, pv = pr == 1 ? 1 : 0;
 #pragma unroll
@@ -305,9 +297,9 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
 #pragma unroll
                         for (int i = 0; i < 4; ++i) mw[q * 1024 + (mb * 4 + i) * 64] = acc[q][mb][i] * unscale;
             }
-            WN_STAMP(4);
+            CT_STAMP(4);
             __syncthreads();
-            WN_STAMP(5);
+            CT_STAMP(5);
             // ---------------- D: (tile dn, couts dc, dc + 32): Y = A^T M A, epilogue, stores ----------------
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -341,9 +333,9 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
                     __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(y[2 * r]), __float_as_uint(y[2 * r + 1])}, out_rs, (int)off, 0, 0);
                 }
             }
-            WN_STAMP(6);
+            CT_STAMP(6);
             __syncthreads();                              // M image consumed (the next transform overwrites it)
-            WN_STAMP(7);
+            CT_STAMP(7);
         };
 #pragma unroll 1
         for (int s = 0; s < steps; s += 3) {
@@ -352,17 +344,8 @@ __global__ __launch_bounds__(kWnThreads, 1) void conv_wino_kernel(ConvArgs a, in
             if (s + 2 < steps) step(s + 2, std::integral_constant<int, 4>());
         }
     }
-#ifdef CT_WN_PROFILE
-    if (lane == 0 && a.prof) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a.prof[((size_t)blockIdx.x * 8 + wave) * 8 + i] = pt[i];
-    }
-#endif
+    CT_STAMPS_WRITE(a.prof, 8, wave, 8);
 }
-
-#ifdef CT_WN_PROFILE
-static unsigned long long *g_wn_prof = nullptr;
-#endif
 
 // which Winograd kernel ct_conv3x3_wino16_f32 launches: 0 = conv_wino4.hip (four waves of 512 registers, pipelined; round 6, the
 // default), 1 = the eight-wave kernel of this file (round 5).  Process-wide, atomic; env CT_HIP_WINO_FORM presets it.
@@ -374,17 +357,9 @@ int conv_wino(const ConvArgs &a, int N, hipStream_t s) {
     if ((unsigned long long)a.H * (unsigned long long)a.W * 64ull * 4ull >= (1ull << 32)) return 1;     // 32-bit byte offsets over 64 planes
     const int n_strips = (a.W + kWnTW - 1) / kWnTW;
     const long long imgs = (long long)N * a.groups;
-    int n_seg = 1, seg = a.H;
-    long long best = -1;
-    for (int ns = 1; ns <= (a.H + 15) / 16; ++ns) {          // even row segments: the split with the fewest steps of the busiest workgroup
-        int sg = (a.H + ns - 1) / ns;
-        sg += sg & 1;
-        const int ns_eff = (a.H + sg - 1) / sg;
-        const long long bands_per_xcd = (imgs * ns_eff + 7) / 8;
-        const long long rounds = (bands_per_xcd * n_strips + 31) / 32;
-        const long long cost = rounds * (sg / 2 + 2);
-        if (best < 0 || cost < best) { best = cost; n_seg = ns_eff; seg = sg; }
-    }
+    // even row segments: the split with the fewest steps of the busiest workgroup
+    const RowSegments rs = pick_row_segments(a.H, imgs, n_strips, true, [](int sg) { return sg / 2 + 2; });
+    const int n_seg = rs.n_seg, seg = rs.seg;
     const long long n_items = imgs * n_seg * n_strips;
     if (n_items > 0x7fffffffLL) return CT_E_BADARG;
     typedef void (*kern_t)(ConvArgs, int, int, int, int);
@@ -395,10 +370,7 @@ int conv_wino(const ConvArgs &a, int N, hipStream_t s) {
     if (attr[actk].ensure(reinterpret_cast<const void *>(kerns[actk]), kWnLds) != hipSuccess) return CT_E_BADARG;
     ConvArgs b = a;
     b.n_images = N;
-#ifdef CT_WN_PROFILE
-    b.prof = g_wn_prof;
-#endif
-    hipLaunchKernelGGL(kerns[actk], dim3(256), dim3(kWnThreads), kWnLds, s, b, n_strips, seg, n_seg, (int)n_items);
+    hipLaunchKernelGGL(kerns[actk], dim3(256), dim3(kWnThreads), kWnLds, s, CT_STAMPS_ARGS(b), n_strips, seg, n_seg, (int)n_items);
     CT_CHECK_LAUNCH();
     return CT_OK;
 }
@@ -413,18 +385,9 @@ extern "C" {
 int ct_conv3x3_wino16_f32(const float *in, const void *wq16, int w_exp, const float *bias, const float *residual, float *out, int n, int cin,
                           int cout, int h, int w, long long in_bstride, long long out_bstride, long long res_bstride, int act, int clamp,
                           void *stream) {
-    if (!in || !wq16 || !bias || !out || n < 0 || cin <= 32 || cin > 64 || cout < 1 || h < 0 || w < 0 || act < 0 || act > 5) return CT_E_BADARG;
-    if ((w % 4) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(wq16) & 15) ||
-        (in_bstride % 4) || (out_bstride % 4) || (residual && ((reinterpret_cast<uintptr_t>(residual) & 15) || (res_bstride % 4))))
-        return CT_E_ALIGN;
-    if (w_exp < -100 || w_exp > 100) return CT_E_BADARG;
+    if (const int rc = ct::conv3x3_16_check(in, wq16, w_exp, bias, residual, out, n, cin, cout, h, w, in_bstride, out_bstride, res_bstride, act)) return rc;
     if (n == 0 || h == 0 || w == 0) return CT_OK;
-    ct::ConvArgs a;
-    a.in = in; a.in2 = nullptr; a.cin1 = cin; a.in2_bstride = 0;
-    a.wp = reinterpret_cast<const float *>(wq16); a.bias = bias; a.residual = residual; a.out = out;
-    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
-    a.in_bstride = in_bstride; a.out_bstride = out_bstride; a.res_bstride = res_bstride;
-    a.act = act; a.clamp = clamp; a.groups = (cout + 63) / 64; a.prof = nullptr;
+    ct::ConvArgs a = ct::conv_args(in, wq16, bias, residual, out, cin, cout, h, w, in_bstride, out_bstride, res_bstride, act, clamp, (cout + 63) / 64);
     a.f16 = 1; a.w_exp = w_exp;
     int rc = 1;
     if (ct::g_wino_form.load(std::memory_order_relaxed) == 0) rc = ct::conv_wino4(a, n, (hipStream_t)stream);   // 1: geometry beyond its 30-bit offsets
@@ -437,9 +400,5 @@ int ct_set_conv_wino_form(int form) {
     ct::g_wino_form.store(form, std::memory_order_relaxed);
     return CT_OK;
 }
-
-#ifdef CT_WN_PROFILE
-void ct_conv_wino_set_prof(unsigned long long *p) { ct::g_wn_prof = p; }
-#endif
 
 }  // extern "C"

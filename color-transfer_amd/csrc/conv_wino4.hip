@@ -22,7 +22,9 @@
 // order (row of positions first), so results are not bitwise those of conv_wino.hip.  Weight image: ct_hip.pack_conv_weight_wino16, unchanged.
 #include "ct_common.h"
 #include "ct_conv.h"
+#include "ct_row_segments.h"
 #include "ct_split.h"
+#include "ct_stamps.h"
 #include <type_traits>
 #include <utility>
 
@@ -330,20 +332,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
     const unsigned int uplane = (unsigned int)(a.H * a.W);
     const size_t plane = (size_t)a.H * a.W;
 
-#ifdef CT_W4_PROFILE
-    // diagnostic build (tools/prof_conv_wino4.py): s_memtime ticks per phase and wave -> a.prof[block][wave][10].  The stamps are
-    // only ISSUED in place (a scalar memory instruction each); their results are awaited once, at the end of the step, so that no
-    // stamp drains the LDS queue in the middle of a phase.
-    unsigned long long pt[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ts[10];
-#define W4_STAMP0() asm volatile("s_memtime %0" : "=s"(ts[9]) :: "memory")
-#define W4_STAMP(i) asm volatile("s_memtime %0" : "=s"(ts[i]) :: "memory")
-#define W4_STAMPS_END() do { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(ts[0]), "+s"(ts[1]), "+s"(ts[2]), "+s"(ts[3]), "+s"(ts[4]), "+s"(ts[5]), "+s"(ts[9]) :: "memory"); \
-        pt[0] += ts[0] - ts[9]; _Pragma("unroll") for (int i__ = 1; i__ < 6; ++i__) pt[i__] += ts[i__] - ts[i__ - 1]; } while (0)
-#else
-#define W4_STAMP0() do { } while (0)
-#define W4_STAMP(i) do { } while (0)
-#define W4_STAMPS_END() do { } while (0)
-#endif
+    CT_STAMPS_BEGIN_DEFERRED(10);     // -DCT_STAMPS (ct_stamps.h, tools/prof_conv.py wino4): s_memtime ticks per phase and wave, deferred form
     St st;
     Ctx cx;
     const u32x4 *wp16 = reinterpret_cast<const u32x4 *>(a.wp);
@@ -571,7 +560,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
         // one step; PAR = s % 2: V image PAR is consumed, image PAR ^ 1 built (step s + 1: pairs s + 1 in set PAR ^ 1, s + 2 in set PAR)
         auto step = [&](int s, auto par_c) {
             constexpr int PAR = decltype(par_c)::value;
-            W4_STAMP0();
+            CT_STAMP_ISSUE0();
             const int oy = y0 + 2 * s;
             const int ex = ex_next;
             const f32x4 mxa = max_of(s + 1), mxb = max_of(s + 2);
@@ -581,7 +570,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
             auto ld = [&](int r, int e, int row, float (&dst)[4]) { load_pair_row(s + 3, r, e, row, dst); };
             // ---------------- phase X: cout blocks 2, 3 of step s; M A of blocks 0, 1; T(s + 1) ----------------
             __builtin_amdgcn_sched_barrier(0);
-            W4_STAMP(0);
+            CT_STAMP_ISSUE(0);
             for_each_c([&](auto c_c) {
                 constexpr int C = decltype(c_c)::value;
                 constexpr const Prog &PX = HAS_RES ? kProgX1 : kProgX0;
@@ -602,7 +591,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
                 for_each_c([&](auto c_c) { mfma(std::integral_constant<int, 1>(), par_c, std::integral_constant<int, 48 - n_tail_slices + decltype(c_c)::value>()); },
                            std::make_integer_sequence<int, n_tail_slices>());
             }
-            W4_STAMP(1);
+            CT_STAMP_ISSUE(1);
             // M A of blocks 2, 3 over the wave's own, consumed, fragments (position 4 w of image PAR).  The last MFMAs wrote
             // acc[3][*] a few cycles ago and the compiler does not know an MFMA when it sees one in asm
             asm volatile("s_nop 15" : "+v"(st.acc[3][0]), "+v"(st.acc[3][1]));
@@ -619,11 +608,11 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
                     }
             }
 #endif
-            W4_STAMP(2);
+            CT_STAMP_ISSUE(2);
 #ifndef W4_ABL_NO_BAR1
             __syncthreads();
 #endif
-            W4_STAMP(3);
+            CT_STAMP_ISSUE(3);
             // ---------------- phase Y: cout blocks 0, 1 of step s + 1; the output side of step s ----------------
             {
                 const float unscale = __uint_as_float((unsigned int)(127 + min(max(-ex - a.w_exp, -126), 127)) << 23);
@@ -642,12 +631,12 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
                     __builtin_amdgcn_sched_barrier(0);
                 }, std::make_integer_sequence<int, 48>());
             }
-            W4_STAMP(4);
+            CT_STAMP_ISSUE(4);
 #ifndef W4_ABL_NO_BAR2
             __syncthreads();
 #endif
-            W4_STAMP(5);
-            W4_STAMPS_END();
+            CT_STAMP_ISSUE(5);
+            CT_STAMPS_AWAIT();
         };
 #pragma unroll 1
         for (int s = 0; s < steps; s += 2) {
@@ -656,19 +645,10 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wino4_kernel(ConvArgs a, int
         }
     }
     asm volatile("" :: "v"(touch));
-#ifdef CT_W4_PROFILE
-    if (lane == 0 && a.prof) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) a.prof[((size_t)blockIdx.x * 4 + wave) * 10 + i] = pt[i];
-    }
-#endif
+    CT_STAMPS_WRITE(a.prof, 4, wave, 10);
 }
 
 }  // namespace w4
-
-#ifdef CT_W4_PROFILE
-static unsigned long long *g_w4_prof = nullptr;
-#endif
 
 // 1 = not this kernel's geometry
 int conv_wino4(const ConvArgs &a, int N, hipStream_t s) {
@@ -677,17 +657,9 @@ int conv_wino4(const ConvArgs &a, int N, hipStream_t s) {
     if ((unsigned long long)a.H * (unsigned long long)a.W * 64ull * 4ull >= (1ull << 30)) return 1;     // 30-bit byte offsets over 64 planes (the kernel's out-of-range marks)
     const int n_strips = (a.W + w4::kTW - 1) / w4::kTW;
     const long long imgs = (long long)N * a.groups;
-    int n_seg = 1, seg = a.H;
-    long long best = -1;
-    for (int ns = 1; ns <= (a.H + 15) / 16; ++ns) {          // even row segments: the split with the fewest steps of the busiest workgroup
-        int sg = (a.H + ns - 1) / ns;
-        sg += sg & 1;
-        const int ns_eff = (a.H + sg - 1) / sg;
-        const long long bands_per_xcd = (imgs * ns_eff + 7) / 8;
-        const long long rounds = (bands_per_xcd * n_strips + 31) / 32;
-        const long long cost = rounds * (sg / 2 + 3);
-        if (best < 0 || cost < best) { best = cost; n_seg = ns_eff; seg = sg; }
-    }
+    // even row segments: the split with the fewest steps of the busiest workgroup
+    const RowSegments rs = pick_row_segments(a.H, imgs, n_strips, true, [](int sg) { return sg / 2 + 3; });
+    const int n_seg = rs.n_seg, seg = rs.seg;
     const long long n_items = imgs * n_seg * n_strips;
     if (n_items > 0x7fffffffLL) return CT_E_BADARG;
     typedef void (*kern_t)(ConvArgs, int, int, int, int);
@@ -698,16 +670,9 @@ int conv_wino4(const ConvArgs &a, int N, hipStream_t s) {
     if (attr[k].ensure(reinterpret_cast<const void *>(kerns[k]), w4::kLds) != hipSuccess) return CT_E_BADARG;
     ConvArgs b = a;
     b.n_images = N;
-#ifdef CT_W4_PROFILE
-    b.prof = g_w4_prof;
-#endif
-    hipLaunchKernelGGL(kerns[k], dim3(256), dim3(w4::kThreads), w4::kLds, s, b, n_strips, seg, n_seg, (int)n_items);
+    hipLaunchKernelGGL(kerns[k], dim3(256), dim3(w4::kThreads), w4::kLds, s, CT_STAMPS_ARGS(b), n_strips, seg, n_seg, (int)n_items);
     CT_CHECK_LAUNCH();
     return CT_OK;
 }
 
 }  // namespace ct
-
-#ifdef CT_W4_PROFILE
-extern "C" void ct_conv_wino4_set_prof(unsigned long long *p) { ct::g_w4_prof = p; }
-#endif

@@ -6,7 +6,7 @@
 // comment at the kernel).  Different dataflow: conv_split shares one input tile between the four waves of a workgroup and
 // streams the weights of every tap through an LDS ring -- one barrier per tap, a conversion phase between the stages, two
 // workgroups per CU competing for the matrix pipe: 47 % MFMA-busy, 22 % of a wave's time in the per-tap barriers, 13 % in the
-// conversion phase (tools/prof_conv_split.py).  Here the contraction is split ACROSS the waves: wave (c, m) of the eight owns
+// conversion phase (tools/prof_conv.py split).  Here the contraction is split ACROSS the waves: wave (c, m) of the eight owns
 // input channels [16 c, 16 c + 16) and output channels [32 m, 32 m + 32) and keeps the weights of all nine taps of that block
 // in registers (18 or 27 fragments = 72 / 108 VGPRs) for the lifetime of a persistent workgroup (one per CU; the two waves of a
 // chunk share a SIMD).  A workgroup walks down a 32-pixel wide strip of a row segment; per output row (a "step") a wave runs
@@ -21,14 +21,15 @@
 // Rounding: float32 sums per chunk, then ((p0 + p1) + p2) + p3 + bias -- float32-grade like conv_split (not bitwise equal).
 #include "ct_common.h"
 #include "ct_conv.h"
+#include "ct_row_segments.h"
 #include "ct_split.h"
+#include "ct_stamps.h"
 #include <type_traits>
 
 namespace ct {
 
 constexpr int kWsTW = 32;                    // output columns of a strip (= MFMA N)
 constexpr int kWsCols = 40;                  // staged columns x0-4 .. x0+35 (ten aligned groups of four)
-constexpr int kWsSlotMax = 3 * 2 * kWsCols;  // 16-byte entries of one input row of one chunk: [piece][k-half][column] (3 bf16 or 2 fp16 pieces)
 constexpr int kWsRing = 4;                   // input rows resident per wave (three in use, one being filled)
 constexpr int kWsPS = 36;                    // floats per row of a partial-sum tile (16-byte aligned; 40 / 44 and s_setprio around X: no change)
 constexpr int kWsChunks = 4;                 // 16-channel chunks = SIMDs
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
     // lane-dependent select both orders shared one loop body, and the compiler -- which must assume that either side's loads can
     // be in flight when the other side starts -- drained the vector memory counter at the head of every step: the wave that
     // starts with X waited for the requests it had issued just before the barrier (a full memory latency per row step),
-    // the one that starts with Y for the store of the previous X (round 5, tools/prof_conv_ws.py)
+    // the one that starts with Y for the store of the previous X (round 5, tools/prof_conv.py ws)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int chunk = wave & 3, mt = wave >> 2;         // waves c and c + 4 run on SIMD c
     uint4 *ring = smem16 + chunk * (kWsRing * kWsSlot);                                   // this chunk's input rows
@@ -74,16 +75,10 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
     const bool u_lane = lane < 40;
     const bool u_on = u_lane && (c_base + 2 * u_cp < a.cin);
 
-#ifdef CT_CONV_PROFILE
-    // diagnostic build (make prof, tools/prof_conv_ws.py): s_memtime ticks per phase, per wave -> a.prof[block][wave][8]
+    // -DCT_STAMPS (ct_stamps.h, tools/prof_conv.py ws): s_memtime ticks per phase, per wave
     // 0 X (reduce of the previous row, MFMAs, partial sums), 1 the step's barrier, 2 Y (requests, row maximum, staging), 4 everything else
-    unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt0;
-#define WS_STAMP0() asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pt0) :: "memory")
-#define WS_STAMP(i) do { unsigned long long t__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__) :: "memory"); pt[i] += t__ - pt0; pt0 = t__; } while (0)
-    WS_STAMP0();
-#else
-#define WS_STAMP(i) do { } while (0)
-#endif
+    CT_STAMPS_BEGIN(8);
+    CT_STAMP0();
     uint4 wreg[9][PIECES];
     int cur_grp = -1;
     const uint4 *wp16 = reinterpret_cast<const uint4 *>(a.wp);
@@ -145,11 +140,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
         };
         auto row_mask = [&](int y, float &ma, float &mb) {      // 1 / 0: the unit's pixels and channels exist
             const int gx = x0 - 4 + 4 * u_grp;
-#ifdef CT_WS_ABL_NOLOAD
-            const bool ok = false;
-#else
             const bool ok = u_on && y >= 0 && y < a.H && gx >= 0 && gx < a.W;
-#endif
             ma = ok ? 1.f : 0.f;
             mb = (ok && c_base + 2 * u_cp + 1 < a.cin) ? 1.f : 0.f;
         };
@@ -189,11 +180,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
                 scale = __uint_as_float((unsigned int)(127 + ex) << 23);
                 if (lane == 0) slot_exp[chunk * kWsRing + slot] = ex;                // both waves of the chunk write the same value
             }
-#ifdef CT_WS_ABL_NOSTAGE
-            if (la.x == 123.456f) {
-#else
             if (u_lane) {
-#endif
                 const int kh2 = u_cp >> 2, wsel = u_cp & 3;
                 unsigned int *d = reinterpret_cast<unsigned int *>(ring + slot * kWsSlot) + ((kh2 * kWsCols + 4 * u_grp) * 4 + wsel);
                 auto pieces = [&](const float (&xa)[4], const float (&xb)[4]) {
@@ -296,22 +283,13 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
             }
         };
         auto reduce_store = [&](int r) {
-#ifdef CT_WS_ABL_NOSTORE
-            const bool ok = e_ok && r >= 0 && r < rows && rvv[0] == 123.456f;
-#else
             const bool ok = e_ok && r >= 0 && r < rows;      // the first X has no row to finish; the last steps may be padding
-#endif
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             const u32x4 v = {__float_as_uint(rvv[0]), __float_as_uint(rvv[1]), __float_as_uint(rvv[2]), __float_as_uint(rvv[3])};
             const unsigned int off = ok ? ((unsigned int)e_row * uplane + (unsigned int)((y0 + r) * a.W + x0 + 4 * e_g)) * 4u : 0xffffffffu;
             __builtin_amdgcn_raw_buffer_store_b128(v, out_rs, (int)off, 0, 0);
         };
         auto reduce_row = [&](int r, const float4 &rv) { reduce_issue(r); reduce_compute(rv); reduce_store(r); };
-#ifdef CT_WS_ABL_NOREDUCE
-#define reduce_issue(r) do { } while (0)
-#define reduce_compute(rv) do { rvv[0] = rv.x; } while (0)
-#define reduce_store(r) do { } while (0)
-#endif
         // X(r): finish output row r-1, the MFMAs of output row y0 + r on this wave's (chunk, half) block, partial sums -> LDS.
         auto phase_x = [&](int r, const float4 &rv) {
             reduce_issue(r - 1);
@@ -356,13 +334,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
                     if constexpr (F16) {
                         const f16x8 bh = __builtin_bit_cast(f16x8, bq[ky][kx][0]), bl = __builtin_bit_cast(f16x8, bq[ky][kx][1]);
                         const f16x8 ah = __builtin_bit_cast(f16x8, wreg[tap][0]), al = __builtin_bit_cast(f16x8, wreg[tap][1]);
-#ifdef CT_WS_ABL_NOMFMA
-                        if (tap == 4) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-                        else { acc[0] += __builtin_bit_cast(float, __builtin_bit_cast(uint4, bl).y) + __builtin_bit_cast(float, __builtin_bit_cast(uint4, ah).x); }
-                        if (false) {
-#else
                         if (tap & 1) {
-#endif
                             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc2, 0, 0, 0);
                             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
                             acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc2, 0, 0, 0);
@@ -377,18 +349,12 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
                         const bf16x8 bl = __builtin_bit_cast(bf16x8, bq[0][kx][PIECES - 1]);
                         const bf16x8 ah = __builtin_bit_cast(bf16x8, wreg[tap][0]), am = __builtin_bit_cast(bf16x8, wreg[tap][1]),
                                      al = __builtin_bit_cast(bf16x8, wreg[tap][PIECES - 1]);
-#ifdef CT_WS_ABL_NOMFMA
-                        if (tap == 4) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-                        else { acc[0] += __builtin_bit_cast(float, __builtin_bit_cast(uint4, bm).x) + __builtin_bit_cast(float, __builtin_bit_cast(uint4, bl).y) +
-                                         __builtin_bit_cast(float, __builtin_bit_cast(uint4, ah).x) + __builtin_bit_cast(float, __builtin_bit_cast(uint4, am).x); }
-#else
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);       // small terms first (as in conv_split)
                         acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc2, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
                         acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc2, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
                         acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc2, 0, 0, 0);
-#endif
                     }
                 }
                 // the previous row's epilogue in the issue slots the matrix pipe leaves free
@@ -396,15 +362,12 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
                 if (ky == 1) reduce_store(r - 1);
                 if constexpr (F16) __builtin_amdgcn_sched_barrier(0);
             }
-            WS_STAMP(6);
+            CT_STAMP(6);
             // lane owns column nl, output channels 32 mt + (i & 3) + 8 (i >> 2) + 4 hl
             float *pw = part + (((r & 1) * kWsChunks + chunk) * 64 + 32 * mt) * kWsPS + nl;
             float unscale = 1.f;
             if constexpr (F16) unscale = __uint_as_float((unsigned int)(127 + min(max(-e_cur - a.w_exp, -126), 127)) << 23);
 #pragma unroll
-#ifdef CT_WS_ABL_NOPART
-            if (acc[0] == 123.456f)
-#endif
             for (int i = 0; i < 16; ++i) pw[((i & 3) + 8 * (i >> 2) + 4 * hl) * kWsPS] = F16 ? (acc[i] + acc2[i]) * unscale : acc[i] + acc2[i];
         };
         auto phase_x_full = [&](int r, auto set_c) {
@@ -417,9 +380,9 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
             constexpr int SET = decltype(set_c)::value;      // r % 3
             fetch_skip(r + 1, rq[(SET + 1) % 3]);                  // consumed by reduce(r+1) inside X(r+2): more than a step from now
             fetch_row(y0 + r + 4, qa[(SET + 2) % 3], qb[(SET + 2) % 3]);
-            WS_STAMP(3);
+            CT_STAMP(3);
             note_row_max((r + 1) & 1, y0 + r + 3, qa[(SET + 1) % 3], qb[(SET + 1) % 3]);   // F16: the row staged in Y(r+1)
-            WS_STAMP(5);
+            CT_STAMP(5);
             stage_row((r + 3) & (kWsRing - 1), y0 + r + 2, qa[SET], qb[SET], r & 1);   // the slot of input row y0+r-1 is free since X(r-1)
         };
         // The two waves of a SIMD run the phases of a step in opposite order -- while one of them is in X (27 or 54 MFMAs) the
@@ -429,11 +392,11 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
         // r & 1 (last read in step r-1); Y(r) writes ring slot r+3 (last read in step r-1), its exponent, and the row
         // maximum (r+1) & 1, and reads the maxima r & 1 (written in step r-1).
         auto step = [&](int r, auto set_c, auto mt_c) {
-            WS_STAMP(4);
-            if constexpr (decltype(mt_c)::value == 0) { phase_x_full(r, set_c); WS_STAMP(0); phase_y(r, set_c); WS_STAMP(2); }
-            else { phase_y(r, set_c); WS_STAMP(2); phase_x_full(r, set_c); WS_STAMP(0); }
+            CT_STAMP(4);
+            if constexpr (decltype(mt_c)::value == 0) { phase_x_full(r, set_c); CT_STAMP(0); phase_y(r, set_c); CT_STAMP(2); }
+            else { phase_y(r, set_c); CT_STAMP(2); phase_x_full(r, set_c); CT_STAMP(0); }
             __syncthreads();
-            WS_STAMP(1);
+            CT_STAMP(1);
         };
         const int steps = (rows + 2) / 3 * 3;
         auto row_loop = [&](auto mt_c) {
@@ -449,25 +412,13 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs a, int n_strip
         reduce_row(steps - 1, rq[2]);                        // steps % 3 == 0: the skip row of the last step sits in set 2
         __syncthreads();      // the partial-sum tiles of the last rows are read before the next item overwrites them
     }
-#ifdef CT_CONV_PROFILE
-    WS_STAMP(4);
-    if (lane == 0 && a.prof) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a.prof[((size_t)blockIdx.x * kWsWaves + wave) * 8 + i] = pt[i];
-    }
-#endif
+    CT_STAMP(4);
+    CT_STAMPS_WRITE(a.prof, kWsWaves, wave, 8);
 }
-
-#ifdef CT_CONV_PROFILE
-static unsigned long long *g_ws_prof = nullptr;     // diagnostic build: every conv_ws launch stamps its phases here
-#endif
 
 // 1 = not this kernel's geometry (the caller falls back to conv_split_kernel)
 int conv_ws(const ConvArgs &a, int N, bool gen, hipStream_t s) {
     static const int enabled = env_int("CT_HIP_CONV_WS", 1);
-#ifndef CT_CONV_PROFILE
-    if (a.prof != nullptr) return 1;
-#endif
     if ((!enabled && !a.f16) || a.in2 != nullptr || a.cin <= 32 || a.cin > 64) return 1;
     if ((unsigned long long)a.H * (unsigned long long)a.W * 64ull >= (1ull << 32)) return 1;     // the kernel indexes a 64-channel image with 32 bits (and eight output planes with 32-bit BYTE offsets): the tile kernel takes larger ones
     const int n_strips = (a.W + kWsTW - 1) / kWsTW;
@@ -475,16 +426,8 @@ int conv_ws(const ConvArgs &a, int N, bool gen, hipStream_t s) {
     // of that XCD; a segment costs its rows + 2 halo rows of staging)
     const long long cols = (long long)N * a.groups * n_strips;
     const long long imgs = (long long)N * a.groups;
-    int n_seg = 1, seg = a.H;
-    long long best = -1;
-    for (int ns = 1; ns <= (a.H + 15) / 16; ++ns) {
-        const int sg = (a.H + ns - 1) / ns;
-        const int ns_eff = (a.H + sg - 1) / sg;
-        const long long bands_per_xcd = (imgs * ns_eff + 7) / 8;
-        const long long rounds = (bands_per_xcd * n_strips + 31) / 32;
-        const long long cost = rounds * ((sg + 2) / 3 * 3 + 2);      // steps run in threes; two halo rows of prologue
-        if (best < 0 || cost < best) { best = cost; n_seg = ns_eff; seg = sg; }
-    }
+    RowSegments rs = pick_row_segments(a.H, imgs, n_strips, false, [](int sg) { return (sg + 2) / 3 * 3 + 2; });   // steps run in threes; two halo rows of prologue
+    int n_seg = rs.n_seg, seg = rs.seg;
     static const int forced_seg = env_int("CT_HIP_WS_SEG", 0);   // tuning only
     if (forced_seg > 0) { seg = forced_seg < a.H ? forced_seg : a.H; n_seg = (a.H + seg - 1) / seg; }
     const long long n_items = cols * n_seg;
@@ -494,9 +437,6 @@ int conv_ws(const ConvArgs &a, int N, bool gen, hipStream_t s) {
     const int grid = 256;       // a multiple of 8 (the XCD-aware item order); idle workgroups leave at once
     ConvArgs b = a;
     b.n_images = N;
-#ifdef CT_CONV_PROFILE
-    if (g_ws_prof) b.prof = g_ws_prof;
-#endif
     const int actk = !gen ? 1 : (a.act >= 0 && a.act <= 2) ? a.act : 3;      // gen == false: the DCMCS3DI entry (LeakyReLU or none)
     const int actk_eff = (!gen && a.act == 0) ? 0 : actk;
     const int variant = (a.f16 ? 4 : 0) + actk_eff;
@@ -509,7 +449,7 @@ int conv_ws(const ConvArgs &a, int N, bool gen, hipStream_t s) {
         hipError_t e = attr[variant].ensure(reinterpret_cast<const void *>(kern), lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kWsWaves), lds, s, b, n_strips, seg, n_seg, (int)n_items);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kWsWaves), lds, s, CT_STAMPS_ARGS(b), n_strips, seg, n_seg, (int)n_items);
     CT_CHECK_LAUNCH();
     return CT_OK;
 }
@@ -524,25 +464,12 @@ extern "C" {
 int ct_conv3x3_ws16_f32(const float *in, const void *wp16, int w_exp, const float *bias, const float *residual, float *out, int n, int cin,
                         int cout, int h, int w, long long in_bstride, long long out_bstride, long long res_bstride, int act, int clamp,
                         void *stream) {
-    if (!in || !wp16 || !bias || !out || n < 0 || cin <= 32 || cin > 64 || cout < 1 || h < 0 || w < 0 || act < 0 || act > 5) return CT_E_BADARG;
-    if ((w % 4) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(wp16) & 15) ||
-        (in_bstride % 4) || (out_bstride % 4) || (residual && ((reinterpret_cast<uintptr_t>(residual) & 15) || (res_bstride % 4))))
-        return CT_E_ALIGN;
-    if (w_exp < -100 || w_exp > 100) return CT_E_BADARG;
+    if (const int rc = ct::conv3x3_16_check(in, wp16, w_exp, bias, residual, out, n, cin, cout, h, w, in_bstride, out_bstride, res_bstride, act)) return rc;
     if (n == 0 || h == 0 || w == 0) return CT_OK;
-    ct::ConvArgs a;
-    a.in = in; a.in2 = nullptr; a.cin1 = cin; a.in2_bstride = 0;
-    a.wp = reinterpret_cast<const float *>(wp16); a.bias = bias; a.residual = residual; a.out = out;
-    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
-    a.in_bstride = in_bstride; a.out_bstride = out_bstride; a.res_bstride = res_bstride;
-    a.act = act; a.clamp = clamp; a.groups = (cout + 63) / 64; a.prof = nullptr;
+    ct::ConvArgs a = ct::conv_args(in, wp16, bias, residual, out, cin, cout, h, w, in_bstride, out_bstride, res_bstride, act, clamp, (cout + 63) / 64);
     a.f16 = 1; a.w_exp = w_exp;
     const int rc = ct::conv_ws(a, n, true, (hipStream_t)stream);
     return rc == 1 ? CT_E_BADARG : rc;
 }
-
-#ifdef CT_CONV_PROFILE
-void ct_conv_ws_set_prof(unsigned long long *p) { ct::g_ws_prof = p; }
-#endif
 
 }  // extern "C"

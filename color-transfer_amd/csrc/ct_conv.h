@@ -1,6 +1,9 @@
-// ct_conv.h -- argument block of the LDS-tiled MFMA convolution (cnn.hip), shared with conv_generic.hip
+// ct_conv.h -- argument block of the MFMA convolution kernels (conv_exact.hip, conv_split.hip, conv_ws.hip, conv_wino*.hip), shared
+// with conv_generic.hip, and the host helpers every launch goes through
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
+#include "../../include/ct_hip.h"
 
 namespace ct {
 
@@ -18,7 +21,7 @@ struct ConvArgs {
     int act;     // 0 none, 1 LeakyReLU(0.01), 2 ReLU, 3 sigmoid, 4 tanh
     int clamp;   // 1 = clamp to [0,1]
     int groups;  // output-channel groups of MT*32 (weights packed group-major); 1 for cout <= 64
-    unsigned long long *prof;   // diagnostic builds only (CT_CONV_PROFILE); NULL otherwise
+    unsigned long long *prof;   // phase stamps of a -DCT_STAMPS build (ct_stamps.h); NULL otherwise
     int n_images = 0;           // conv_ws only (set by its launcher)
     const float *in3 = nullptr;  // split kernel only: channels >= cin2 come from this tensor (a third torch.cat operand); cin2 % 16 == 0
     int cin2 = 0;
@@ -37,6 +40,29 @@ struct ConvArgs {
                                     //     by a producer that came too late for its consumer cannot satisfy the next launch's wait)
 };
 
+// The fields every entry point fills; the rest keep their defaults (one input tensor, no stamps).
+inline ConvArgs conv_args(const float *in, const void *wp, const float *bias, const float *residual, float *out, int cin, int cout, int h,
+                          int w, long long in_bstride, long long out_bstride, long long res_bstride, int act, int clamp, int groups) {
+    ConvArgs a;
+    a.in = in; a.in2 = nullptr; a.cin1 = cin; a.in2_bstride = 0;
+    a.wp = reinterpret_cast<const float *>(wp); a.bias = bias; a.residual = residual; a.out = out;
+    a.cin = cin; a.cout = cout; a.H = h; a.W = w;
+    a.in_bstride = in_bstride; a.out_bstride = out_bstride; a.res_bstride = res_bstride;
+    a.act = act; a.clamp = clamp; a.groups = groups; a.prof = nullptr;
+    return a;
+}
+
+// Argument and alignment checks of the two 16-bit-form 3x3 entries (ct_conv3x3_ws16_f32, ct_conv3x3_wino16_f32): CT_OK or the error
+inline int conv3x3_16_check(const float *in, const void *wp16, int w_exp, const float *bias, const float *residual, const float *out, int n,
+                            int cin, int cout, int h, int w, long long in_bstride, long long out_bstride, long long res_bstride, int act) {
+    if (!in || !wp16 || !bias || !out || n < 0 || cin <= 32 || cin > 64 || cout < 1 || h < 0 || w < 0 || act < 0 || act > 5) return CT_E_BADARG;
+    if ((w % 4) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(wp16) & 15) ||
+        (in_bstride % 4) || (out_bstride % 4) || (residual && ((reinterpret_cast<uintptr_t>(residual) & 15) || (res_bstride % 4))))
+        return CT_E_ALIGN;
+    if (w_exp < -100 || w_exp > 100) return CT_E_BADARG;
+    return CT_OK;
+}
+
 struct GConvArgs {
     const float *in, *wp, *bias;   // wp: [coutp/64][kh*kw][cin_pairs][2][64], coutp = 64*ceil(cout/64); bias padded to coutp (or null)
     float *out;
@@ -51,7 +77,7 @@ struct GConvArgs {
 //   cin <= 3, kernel <= 7x7, stride 1 or 2 (its 7x7 stem 3 -> 64 and the motion encoder's 7x7 on the 2-channel flow)
 int conv_direct(const GConvArgs &a, int N, hipStream_t s);
 
-// cnn.hip: stride-1, padding k/2, kernel 3x3 / 1x1 / 1x5 / 5x1, weights packed [group][tap][cin_pair][2][64];
+// conv_exact.hip: stride-1, padding k/2, kernel 3x3 / 1x1 / 1x5 / 5x1, weights packed [group][tap][cin_pair][2][64];
 // returns CT_OK / an error, or 1 if (kh, kw) has no LDS-tiled kernel
 int conv_fast(const ConvArgs &a, int N, int kh, int kw, hipStream_t s);
 

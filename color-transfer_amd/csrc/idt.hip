@@ -261,11 +261,9 @@ __device__ __forceinline__ double idt_edge(int i, int bins, double lo, double hi
 __device__ __forceinline__ int idt_bin(double x, int bins, double lo, double hi, double step, double scale) {
     int k = (int)((x - lo) * scale);
     k = k < 0 ? 0 : (k > bins - 1 ? bins - 1 : k);
-#ifndef CT_IDT_NO_FASTBIN
     // k <= bins - 1: edge k is never the special last edge, and edge k + 1 only matters when it is not (k < bins - 1)
     const bool settled = (x >= (double)k * step + lo) & ((k == bins - 1) | (x < (double)(k + 1) * step + lo));
     if (__builtin_amdgcn_ballot_w64(!settled) == 0) return k;
-#endif
 #pragma unroll
     for (int rep = 0; rep < 2; ++rep) {
         if (x < idt_edge(k, bins, lo, hi, step)) k -= (k > 0);

@@ -184,14 +184,6 @@ __global__ __launch_bounds__(256) void layernorm_tokens_kernel(const float *__re
 // K % 32 == 0.
 // =================================================================================================
 constexpr int kLsW = 3 * 4 * 128;                 // uint4 entries of the W image (= one packed chunk)
-#ifdef CT_LS_PROFILE
-// diagnostic build (tools/build_variant.sh, never shipped): per-phase s_memtime totals of wave 0 of every workgroup
-__device__ unsigned long long g_ls_prof[8];
-#define LS_STAMP(var) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory")
-#define LS_PHASE(i) do { unsigned long long t__; LS_STAMP(t__); pt[i] += t__ - pt0; pt0 = t__; } while (0)
-#else
-#define LS_PHASE(i) do { } while (0)
-#endif
 
 template <int MT>
 __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__restrict__ x, const float *__restrict__ x2, int K1,
@@ -229,9 +221,6 @@ __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__res
         const bool second = kc >= K1;          // uniform: a 32-channel chunk never straddles the two sources
         const float *xs = second ? x2 + (kc - K1) + 8 * sg : x + kc + 8 * sg;
         const int ld = second ? K2 : K1;
-#ifdef CT_LS_NOXLOAD
-        if (c > 1) return;
-#endif
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const float4 *p = reinterpret_cast<const float4 *>(xs + xr[i] * ld);
@@ -240,9 +229,6 @@ __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__res
         }
     };
     auto fetch_w = [&](int c) {
-#ifdef CT_LS_NOWLOAD
-        if (c > 1) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 6; ++j) pw[j] = wsrc[(size_t)c * kLsW + 256 * j];
     };
@@ -256,9 +242,6 @@ __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__res
         d[8 * XR] = l;
     };
     auto store_w = [&]() {
-#ifdef CT_LS_NOWSTORE
-        if (pw[0].x != 0x12345u) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 6; ++j) Ws[tid + 256 * j] = pw[j];
     };
@@ -271,10 +254,6 @@ __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__res
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-#ifdef CT_LS_PROFILE
-    unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt0;
-    LS_STAMP(pt0);
-#endif
     fetch_x(0, pb);
     fetch_w(0);
 #pragma unroll
@@ -284,15 +263,11 @@ __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__res
         fetch_x(1, pa);
         fetch_w(1);
     }
-    LS_PHASE(0);                               // prologue
     const int xoff = hl * XR + wm * (MT / 2) + nl;
     const uint4 *wb = Ws + hl * 128 + wn * 64 + nl;
     // one chunk: `cur` holds the raw X of chunk c+1 (loaded a chunk ago), `nxt` receives chunk c+2
     auto chunk = [&](int c, float4 (&cur)[MI][2], float4 (&nxt)[MI][2]) {
-#ifndef CT_LS_NOBAR
         __syncthreads();                       // X image c & 1 and the W image hold chunk c
-#endif
-        LS_PHASE(1);
         if (c + 2 < n_chunks) fetch_x(c + 2, nxt);
         const uint4 *xa = lds + (c & 1) * XIMG + xoff;
         uint4 *xn = lds + ((c + 1) & 1) * XIMG;
@@ -321,16 +296,11 @@ __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__res
                 }
             }
         }
-        LS_PHASE(2);
-#ifndef CT_LS_NOBAR
         __syncthreads();                       // every wave is done with the W image
-#endif
-        LS_PHASE(3);
         if (c + 1 < n_chunks) {
             store_w();
             if (c + 2 < n_chunks) fetch_w(c + 2);
         }
-        LS_PHASE(4);
     };
     for (int c = 0; c < n_chunks; c += 2) {    // unrolled by two: the raw-X register sets swap roles without copies
         chunk(c, pa, pb);
@@ -376,13 +346,6 @@ __global__ __launch_bounds__(256, 2) void linear_split_kernel(const float *__res
                 }
             }
         }
-#ifdef CT_LS_PROFILE
-    LS_PHASE(5);                               // epilogue
-    if (tid == 0) {
-        for (int i = 0; i < 7; ++i) atomicAdd(&g_ls_prof[i], pt[i]);
-        atomicAdd(&g_ls_prof[7], 1ull);
-    }
-#endif
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -502,14 +465,6 @@ int ct_linear_tokens_f32(const float *x, const float *x2, int k1, const float *w
     return CT_OK;
 }
 
-#ifdef CT_LS_PROFILE
-int ct_debug_ls_prof(unsigned long long *host8, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return CT_E_BADARG;
-    if (host8 && hipMemcpyFromSymbol(host8, HIP_SYMBOL(ct::g_ls_prof), 64) != hipSuccess) return CT_E_BADARG;
-    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(ct::g_ls_prof), z, 64) != hipSuccess) return CT_E_BADARG; }
-    return CT_OK;
-}
-#endif
 // wp: ct_hip.pack_linear_weight_split(weight): bf16 bit patterns [ceil(n/128)][k/32][piece hi/mid/lo][8-channel group 0..3]
 // [feature row 0..127][8 channels], zero rows beyond n.  k % 32 == 0 (k1 % 32 == 0 with x2).
 int ct_linear_tokens_split_f32(const float *x, const float *x2, int k1, const void *wp, const float *bias, float *out, long long tokens,
@@ -521,7 +476,6 @@ int ct_linear_tokens_split_f32(const float *x, const float *x2, int k1, const vo
     const int n_nt = (n + 127) / 128;
     // 64-token tiles while 128-token tiles would leave CUs without a workgroup (2 per CU are resident)
     const long long tiles128 = (tokens + 127) / 128 * n_nt;
-#ifndef CT_LS_NOWRES
     if (k == 128 && n <= 128 && !x2) {              // q / k / v / merge projections: W resident in LDS, X straight into MFMA fragments
         const long long tiles32 = (tokens + 31) / 32;
         long long g = (tiles32 + 7) / 8;
@@ -531,7 +485,6 @@ int ct_linear_tokens_split_f32(const float *x, const float *x2, int k1, const vo
         CT_CHECK_LAUNCH();
         return CT_OK;
     }
-#endif
     if (tiles128 >= 2 * 256) {
         hipLaunchKernelGGL(ct::linear_split_kernel<128>, dim3((unsigned)tiles128), dim3(256), 0, (hipStream_t)stream, x, x2, k1,
                            (const uint4 *)wp, bias, out, tokens, k, n, act, n_nt);

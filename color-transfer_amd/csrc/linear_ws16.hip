@@ -83,9 +83,6 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
     float4 raw[4][4];
     uint4 fb[2][2][2];                             // B fragments [chunk parity][K step][piece]
     auto fetch = [&](const float4 *p, int c, float4 (&r)[4]) {
-#ifdef CT_W16_ABL_NOLOAD
-        if (tile != t_begin + wave) return;
-#endif
 #pragma unroll
         for (int q = 0; q < 4; ++q) r[q] = p[4 * c + q];
     };
@@ -217,9 +214,7 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
                         const float4 b4 = *reinterpret_cast<const float4 *>(bias + 32 * j + 8 * g + 4 * hl);
                         v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
                     }
-#ifndef CT_W16_ABL_NOGELU
                     if (a.act == 6) { v.x = gelu_as(v.x); v.y = gelu_as(v.y); v.z = gelu_as(v.z); v.w = gelu_as(v.w); }
-#endif
                 }
                 stg[nl * 8 + ((2 * g + hl) ^ (nl & 7))] = v;
             }
@@ -228,11 +223,7 @@ __global__ __launch_bounds__(512, 1) void linear_ws16_kernel(Ws16Args a) {
             for (int q = 0; q < 4; ++q) {
                 const int tk = (lane >> 3) + 8 * q, c4 = lane & 7;
                 float4 v = stg[tk * 8 + (c4 ^ (tk & 7))];
-#ifdef CT_W16_ABL_NOSTORE
-                if (tbase + tk < a.T && v.x == 123.456f) {
-#else
                 if (tbase + tk < a.T) {
-#endif
                     if (NCH == 4 && a.ln_res) {
                         const float4 r4 = *reinterpret_cast<const float4 *>(a.ln_res + (tbase + tk) * 128 + 32 * j + 4 * c4);
                         v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;

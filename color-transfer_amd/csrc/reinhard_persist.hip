@@ -178,11 +178,7 @@ __device__ __forceinline__ void exact_moments_tile(const T *tile, const float (&
 template <typename T, bool PARK, bool STATS = true>
 __device__ __forceinline__ bool fwd_tile(const unsigned char *tab, Scratch *sc, const void *tile, typename Tile<T>::Raw &cur, const float (&kf)[3],
                                          float (&sf)[6], uint32_t *slot, int w, int lane) {
-#ifdef CT_RP_NOEXACT
-    const bool raw = false;
-#else
     const bool raw = !Tile<T>::in_range(cur);
-#endif
     if constexpr (sizeof(T) == 4) {
         if (raw) {                       // some value outside [0, 1] or NaN: moments by the exact code
             if (STATS) exact_moments_tile<T>(reinterpret_cast<const T *>(tile), kf, &sc->side[w][0], lane);
@@ -224,12 +220,8 @@ __device__ __forceinline__ bool fwd_tile(const unsigned char *tab, Scratch *sc, 
         }
         CT_RP_PIXEL_FENCE(q);
     }
-#ifdef CT_RP_NOEXACT
-    return false;
-#else
     // (the statistics keep the float32 value of a pixel next to the kink: 3.4e-7 on one pixel of two million)
     return PARK && __builtin_amdgcn_ballot_w64(near) != 0;
-#endif
 }
 
 // ---- affine map + inverse transform of one parked tile, result stored, squared error against gv accumulated ----------------------
@@ -255,9 +247,6 @@ __device__ __forceinline__ void apply_tile(const unsigned char *tab, const Scrat
         if constexpr (sizeof(T) == 4) return gv.e[i]; else return sc->lut255[byte_of(gv.d, i)];
     };
     bool slow = raw || coef_bad;
-#ifdef CT_RP_NOEXACT
-    slow = false;
-#endif
     if (!slow) {
         bool near = false;
 #pragma unroll
@@ -275,9 +264,7 @@ __device__ __forceinline__ void apply_tile(const unsigned char *tab, const Scrat
             }
             CT_RP_PIXEL_FENCE(q);
         }
-#ifndef CT_RP_NOEXACT
         slow = __builtin_amdgcn_ballot_w64(near) != 0;      // a pixel within rounding of the kink of the inverse: the tile again, exactly
-#endif
     }
     if (slow) {                          // exact float64 code from the pixels in memory (the tile was fetched a stage ago at most)
         e = 0.f;

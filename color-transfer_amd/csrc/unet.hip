@@ -1,5 +1,5 @@
 // unet.hip -- the layers of DMSCT's colour-correction network (methods/dmsct.py:34-56: segmentation_models_pytorch
-// EfficientNet-B2 encoder + U-Net decoder) that the convolution kernels of cnn.hip / conv_split.hip / conv_generic.hip do not
+// EfficientNet-B2 encoder + U-Net decoder) that the convolution kernels of conv_exact.hip / conv_split.hip / conv_generic.hip do not
 // cover, on gfx950.  float32 NCHW.  (smp / efficientnet_pytorch are third-party and absent offline: oracle/smp_unet.py
 // restates their published structure, "parity unpinned".)
 //

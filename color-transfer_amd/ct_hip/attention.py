@@ -1,4 +1,4 @@
-"""Attention (csrc/cnn.hip, attention_tokens.hip, attention16.hip): DCMCS3DI's parallax attention (dense and
+"""Attention (csrc/pam.hip, attention_tokens.hip, attention16.hip): DCMCS3DI's parallax attention (dense and
 streaming, token rows) and GMFlow's token / window attention."""
 import ctypes
 

@@ -1,4 +1,4 @@
-"""Convolutions (csrc/cnn.hip, conv_split.hip, conv_ws.hip, conv_wino*.hip, conv1x1_rows.hip, conv_generic.hip): the arithmetic
+"""Convolutions (csrc/conv_exact.hip, conv_split.hip, conv_ws.hip, conv_wino*.hip, conv1x1_rows.hip, conv_generic.hip): the arithmetic
 switches, ONE dispatch (_conv_entry) and the three front doors conv2d, conv2d_rows and gconv2d."""
 import os
 
@@ -27,7 +27,7 @@ SIGNATURES.update({
 
 # ---- convolution arithmetic --------------------------------------------------------------------------------------
 # "split": float32 operands as three bf16 pieces, six bf16 MFMAs per product (csrc/conv_split.hip; float32-grade
-#          accuracy, 2.67x the matrix rate).  "exact": v_mfma_f32_32x32x2_f32, bitwise an fmaf chain (csrc/cnn.hip).
+#          accuracy, 2.67x the matrix rate).  "exact": v_mfma_f32_32x32x2_f32, bitwise an fmaf chain (csrc/conv_exact.hip).
 # Geometries the split kernel does not cover (stride 2, 7x7, W % 4 != 0, unaligned views) always run "exact".
 _conv_mode = os.environ.get("CT_HIP_CONV", "split")
 # split mode: two fp16 pieces / three MFMAs per product (power-of-two scales per layer and per staged tile / row) instead of three

@@ -2,7 +2,7 @@
 
 `ResB` keeps the reference's attribute tree -- `body.0` conv3x3, `body.1` LeakyReLU, `body.2` conv3x3 -- because those
 names are the state_dict contract (reference checkpoints load strictly); its arithmetic, and that of every plain
-Conv2d of the network, runs in ct_conv2d_split_f32 / ct_conv2d_f32 (csrc/conv_split.hip, csrc/cnn.hip) on weights
+Conv2d of the network, runs in ct_conv2d_split_f32 / ct_conv2d_f32 (csrc/conv_split.hip, csrc/conv_exact.hip) on weights
 re-packed into MFMA operand order once per parameter version.  There is no eager / CPU forward.
 """
 import torch

@@ -15,7 +15,7 @@ all 1920 columns -- every column strip of every kernel and both side edges -- ar
                       N = 1 (the one-view launches of the transfer ResBs at batch 1; methods/dcmcs3di.py:112-114):
                              8 segments of 136 rows -> boundaries 136 / 272 / ...
                     so rows 269|270 and 271|272 both lie inside the band.  (At batch 2 the launches see N = 4 and N = 2: segments
-                    of 540 and 270 rows.)  In `split-ws` mode the same convolutions run on conv_ws.hip, in `exact` on cnn.hip.
+                    of 540 and 270 rows.)  In `split-ws` mode the same convolutions run on conv_ws.hip, in `exact` on conv_exact.hip.
 
 Held per band and mode, max-abs against the oracle: fea_left, fea_right, fea_warped, warped_rgb <= 1e-4 (the project's gate,
 SURVEY 8c); pre_clamp and corrected <= 1e-4 against the oracle's transfer branch fed the DEVICE's valid mask (the threshold
