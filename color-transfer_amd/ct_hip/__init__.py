@@ -22,6 +22,7 @@ from .linear import (CT_LAB_EXACT, CT_LAB_TABLE, affine3x3, lab_mode, lab_stats,
 from .metrics import (CT_WS_FSIM, DISTORTIONS, distort_u8, fft2d_, frame_fsim, frame_icid, frame_psnr, frame_ssim, regrain,
                       _fsim_tables)
 from .idt import IdtDebug, idt, idt_u8
+from .grading import acg_u8, regrain_u8
 from .resize_pack import CT_PACK_CHW, CT_PACK_HWC, PACK_LAYOUTS, bicubic_resize, bilinear_resize, pack_u8, resize_geometry
 from .packing import (ConvSource, SplitOperands, pack_conv_weight, pack_conv_weight_split, pack_conv_weight_split16,
                       pack_conv_weight_wino16, pack_gconv_weight, pack_linear_weight_split, pack_linear_weight_ws16)

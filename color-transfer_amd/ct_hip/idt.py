@@ -78,19 +78,70 @@ def idt(target, reference, rotations, bins=255, round_dr_f32=None, out=None, deb
 _U8_OUT = (torch.uint8, torch.float32, torch.float64)
 
 
-def _u8_frames(t, name):
-    """a uint8 [H,W,3] / [B,H,W,3] device tensor -> its [B,H,W,3] view; every argument error is raised here"""
+def _u8_frames(t, name, fn="idt_u8", dtype=torch.uint8):
+    """a [H,W,3] / [B,H,W,3] device tensor of `dtype` (the uint8 frames) -> its [B,H,W,3] view; every argument error is raised here"""
     if not isinstance(t, torch.Tensor):
-        raise CtHipError("idt_u8: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype != torch.uint8:
-        raise CtHipError("idt_u8: %s must be uint8, got %s" % (name, t.dtype))
+        raise CtHipError("%s: %s must be a tensor, got %s" % (fn, name, type(t).__name__))
+    if t.dtype != dtype:
+        raise CtHipError("%s: %s must be %s, got %s" % (fn, name, str(dtype).replace("torch.", ""), t.dtype))
     x, _ = _as_batch(t)
     if x.shape[-1] != 3:
-        raise CtHipError("idt_u8: %s must be [H,W,3] or [B,H,W,3], got %s" % (name, tuple(t.shape)))
+        raise CtHipError("%s: %s must be [H,W,3] or [B,H,W,3], got %s" % (fn, name, tuple(t.shape)))
     if x.numel() == 0:
-        raise CtHipError("idt_u8: %s is empty %s" % (name, tuple(t.shape)))
+        raise CtHipError("%s: %s is empty %s" % (fn, name, tuple(t.shape)))
     _require_cuda(x)
     return x
+
+
+def _u8_outputs(x, out, out_dtype, fn):
+    """the `out` / `out_dtype` rule of the uint8 entries -> (the tensors as given, {dtype: tensor})"""
+    outs = list(out) if isinstance(out, (tuple, list)) else [out]
+    if out is None:
+        if out_dtype not in _U8_OUT:
+            raise CtHipError("%s writes uint8, float32 or float64, not %s (out_dtype)" % (fn, out_dtype))
+        outs = [torch.empty(x.shape, dtype=out_dtype, device=x.device)]
+    slots = {}
+    for o in outs:
+        if not isinstance(o, torch.Tensor) or o.dtype not in _U8_OUT:
+            raise CtHipError("%s: out takes uint8, float32 or float64 tensors, got %s" % (fn, getattr(o, "dtype", type(o).__name__)))
+        _require_cuda(o)
+        if o.device != x.device:
+            raise CtHipError("%s: out is on %s, the input on %s" % (fn, o.device, x.device))
+        if o.numel() != x.numel():
+            raise CtHipError("%s: out has %d elements, the target %d" % (fn, o.numel(), x.numel()))
+        if o.dtype in slots:
+            raise CtHipError("%s: two outputs (out) of dtype %s" % (fn, o.dtype))
+        slots[o.dtype] = o
+    if not slots:
+        raise CtHipError("%s needs at least one output (out)" % fn)
+    return outs, slots
+
+
+def _u8_metric(x, gt, psnr_out, fn):
+    """the gt / psnr_out rule of the uint8 entries -> (the [B,H,W,3] view of gt, psnr_out), or (None, None) without gt"""
+    if gt is None:
+        if psnr_out is not None:
+            raise CtHipError("%s: psnr_out without gt" % fn)
+        return None, None
+    g = _u8_frames(gt, "gt", fn)
+    if g.shape != x.shape or g.device != x.device:
+        raise CtHipError("%s: gt must be uint8 frames of the target's shape and device, got %s on %s" % (fn, tuple(g.shape), g.device))
+    B = x.shape[0]
+    if psnr_out is None:
+        psnr_out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    if not isinstance(psnr_out, torch.Tensor):
+        raise CtHipError("%s: psnr_out must be a tensor" % fn)
+    _require_cuda(psnr_out)
+    if psnr_out.dtype != torch.float64 or psnr_out.numel() < 2 * B or psnr_out.device != x.device:
+        raise CtHipError("%s: psnr_out must be float64 with >= 2*B elements on the input's device" % fn)
+    return g, psnr_out
+
+
+def _u8_rotations(rotations, B, fn):
+    rot = rotations.detach().cpu().numpy() if isinstance(rotations, torch.Tensor) else np.asarray(rotations)
+    if rot.ndim not in (3, 4) or rot.shape[-2:] != (3, 3) or rot.shape[-3] < 1 or (rot.ndim == 4 and rot.shape[0] != B):
+        raise CtHipError("%s: rotations must be [n_iter,3,3] or [B,n_iter,3,3] with n_iter >= 1, got %s" % (fn, tuple(rot.shape)))
+    return rot
 
 
 def idt_u8(target, reference, rotations, bins=255, input_f32=True, round_dr_f32=None, out_dtype=torch.uint8, out=None, gt=None,
@@ -112,45 +163,12 @@ def idt_u8(target, reference, rotations, bins=255, input_f32=True, round_dr_f32=
     B, n_t, n_r = x.shape[0], x.shape[1] * x.shape[2], r.shape[1] * r.shape[2]
     if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= 1024:
         raise CtHipError("idt_u8: bins must be an integer in 1..1024, got %r" % (bins,))
-    rot = rotations.detach().cpu().numpy() if isinstance(rotations, torch.Tensor) else np.asarray(rotations)
-    if rot.ndim not in (3, 4) or rot.shape[-2:] != (3, 3) or rot.shape[-3] < 1 or (rot.ndim == 4 and rot.shape[0] != B):
-        raise CtHipError("idt_u8: rotations must be [n_iter,3,3] or [B,n_iter,3,3] with n_iter >= 1, got %s" % (tuple(rot.shape),))
+    rot = _u8_rotations(rotations, B, "idt_u8")
     if round_dr_f32 is None:
         round_dr_f32 = input_f32
-    outs = list(out) if isinstance(out, (tuple, list)) else [out]
-    if out is None:
-        if out_dtype not in _U8_OUT:
-            raise CtHipError("idt_u8 writes uint8, float32 or float64, not %s" % (out_dtype,))
-        outs = [torch.empty(x.shape, dtype=out_dtype, device=x.device)]
-    slots = {}
-    for o in outs:
-        if not isinstance(o, torch.Tensor) or o.dtype not in _U8_OUT:
-            raise CtHipError("idt_u8 writes uint8, float32 or float64 tensors, got %s" % (getattr(o, "dtype", type(o).__name__),))
-        _require_cuda(o)
-        if o.device != x.device:
-            raise CtHipError("out is on %s, the input on %s" % (o.device, x.device))
-        if o.numel() != x.numel():
-            raise CtHipError("out has %d elements, the target %d" % (o.numel(), x.numel()))
-        if o.dtype in slots:
-            raise CtHipError("idt_u8: two outputs of dtype %s" % o.dtype)
-        slots[o.dtype] = o
-    if not slots:
-        raise CtHipError("idt_u8 needs at least one output")
+    outs, slots = _u8_outputs(x, out, out_dtype, "idt_u8")
     null = ctypes.c_void_p(0)
-    g = None
-    if gt is not None:
-        g = _u8_frames(gt, "gt")
-        if g.shape != x.shape or g.device != x.device:
-            raise CtHipError("gt must be uint8 frames of the target's shape and device, got %s on %s" % (tuple(g.shape), g.device))
-        if psnr_out is None:
-            psnr_out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
-        if not isinstance(psnr_out, torch.Tensor):
-            raise CtHipError("psnr_out must be a tensor")
-        _require_cuda(psnr_out)
-        if psnr_out.dtype != torch.float64 or psnr_out.numel() < 2 * B or psnr_out.device != x.device:
-            raise CtHipError("psnr_out must be float64 with >= 2*B elements on the input's device")
-    elif psnr_out is not None:
-        raise CtHipError("psnr_out without gt")
+    g, psnr_out = _u8_metric(x, gt, psnr_out, "idt_u8")
     both, n_iter = _upload_rotations(rot, B, x.device)
     need = lib().ct_idt_u8_workspace_bytes(B, n_iter, bins, n_t, 0 if torch.float64 in slots else 1)
     if need == 0:

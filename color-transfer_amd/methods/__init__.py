@@ -88,19 +88,23 @@ REINHARD_SPEC = "methods.linear.color_transfer_between_images"
 MK_SPEC = "methods.linear.monge_kantorovitch_color_transfer"
 XIAO_SPEC = "methods.linear.color_transfer_in_correlated_color_space"
 IDT_SPEC = "methods.iterative.iterative_distribution_transfer"
+ACG_SPEC = "methods.iterative.automated_color_grading"
 
 
 class Runner(torch.nn.Module):
-    def __init__(self, func_spec, metrics=None, byte_groups=False, iterative_groups=False):
+    def __init__(self, func_spec, metrics=None, byte_groups=False, iterative_groups=False, grading_groups=False):
         """func_spec: the reference's only argument (methods/__init__.py:12).  metrics (not in the reference): which of psnr, ssim,
         fsim, icid test_step computes -- default all four, like the reference; `psnr` alone lets the Reinhard transfer take its
         fused uint8 entry (test_group).  byte_groups (not in the reference; `--model.byte_groups true`): with `psnr` alone, MK
         (default decomposition) and Xiao take whole groups of uint8 frames as well, and predict_group hands out bytes.
         iterative_groups (not in the reference; `--model.iterative_groups true`): with `psnr` alone, the iterative distribution
-        transfer takes whole groups of uint8 frames (ct_hip.idt_u8, one draw of rotations per frame in frame order)."""
+        transfer takes whole groups of uint8 frames (ct_hip.idt_u8, one draw of rotations per frame in frame order).
+        grading_groups (not in the reference; `--model.grading_groups true`): the same for automated_color_grading (ct_hip.acg_u8:
+        the grouped IDT, then the regrain of the whole group in the launches of one frame)."""
         super().__init__()
         self.byte_groups = bool(byte_groups)
         self.iterative_groups = bool(iterative_groups)
+        self.grading_groups = bool(grading_groups)
         specs = func_spec.split(".")
         module, func = ".".join(specs[:-1]), specs[-1]
         mod = importlib.import_module(module)
@@ -117,11 +121,13 @@ class Runner(torch.nn.Module):
         """True when whole groups of uint8 frames go through test_group / predict_group, which needs PSNR as the only metric: the
         Reinhard transfer (ONE fused call: ct_reinhard_psnr_u8 reads the bytes; k / 255 and its gamma expansion come from tables
         inside the kernel), with byte_groups MK in its default decomposition (ct_mk_u8) and Xiao (its pieces on bytes), and with
-        iterative_groups the iterative distribution transfer (ct_idt_u8)."""
+        iterative_groups the iterative distribution transfer (ct_idt_u8), with grading_groups automated_color_grading (ct_acg_u8)."""
         if self.metrics != ("psnr",):
             return False
         if self.func_spec == IDT_SPEC:
             return self.iterative_groups
+        if self.func_spec == ACG_SPEC:
+            return self.grading_groups
         return self.func_spec == REINHARD_SPEC or (self.byte_groups and self.func_spec in (MK_SPEC, XIAO_SPEC))
 
     def test_group(self, group_u8, psnr_out):
@@ -138,6 +144,10 @@ class Runner(torch.nn.Module):
             # one draw per frame in frame order, like forward()'s loop: a seeded np.random gives the per-frame route's matrices
             from methods.iterative import draw_group_rotations
             ct_hip.idt_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out=out, gt=group_u8[2], psnr_out=psnr_out)
+            return out
+        if self.func_spec == ACG_SPEC:
+            from methods.iterative import draw_group_rotations
+            ct_hip.acg_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out=out, gt=group_u8[2], psnr_out=psnr_out)
             return out
         if self.func_spec == MK_SPEC:
             ct_hip.mk(group_u8[0], group_u8[1], out=out, gt=group_u8[2], psnr_out=psnr_out)
@@ -158,6 +168,9 @@ class Runner(torch.nn.Module):
         if self.func_spec == IDT_SPEC:
             from methods.iterative import draw_group_rotations
             return ct_hip.idt_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out_dtype=torch.uint8)
+        if self.func_spec == ACG_SPEC:
+            from methods.iterative import draw_group_rotations
+            return ct_hip.acg_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out_dtype=torch.uint8)
         if self.func_spec != REINHARD_SPEC:
             return self.func_cuda(group_u8[0], group_u8[1], out_dtype=torch.uint8)
         if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:

@@ -12,7 +12,8 @@ independent frame sharding).  No CPU fallback.  `iterative_distribution_transfer
 
 `automated_color_grading(target, reference)` (iterative.py:118-138) = IDT followed by `_regrain` (iterative.py:62-117:
 multigrid gradient-preserving relaxation over a skimage.transform.resize pyramid), both on the device
-(ct_idt_* + ct_regrain_f64); returns float64 like the reference.
+(ct_idt_* + ct_regrain_f64); returns float64 like the reference.  `automated_color_grading_cuda` also takes uint8 device frames,
+a whole group per call (ct_acg_u8: bytes in, float64 / float32 / bytes out).
 """
 import numpy as np
 import scipy
@@ -93,8 +94,17 @@ def iterative_distribution_transfer(target, reference, bins=255, n_iter=4, rotat
     return out.cpu().numpy().reshape(shape)
 
 
-def automated_color_grading_cuda(target, reference, rotations=None, nbits=(4, 16, 32, 64, 64, 64)):
-    """Device-resident automated_color_grading: CUDA tensors [H,W,3] in, float64 [H,W,3] out (asynchronous)."""
+def automated_color_grading_cuda(target, reference, rotations=None, nbits=(4, 16, 32, 64, 64, 64), out=None, input_f32=True, out_dtype=None):
+    """Device-resident automated_color_grading: CUDA tensors [H,W,3] in, float64 [H,W,3] out (asynchronous).  uint8 frames
+    [H,W,3] / [B,H,W,3] go to ct_hip.acg_u8, a whole group per call: the bytes stand for float32(k) / 255 (input_f32, what a
+    Runner makes of a frame) or for k / 255.0, and the result is float64 (default), float32 or bytes (out_dtype); without
+    `rotations` a batch draws per frame, in frame order."""
+    if target.dtype == torch.uint8:
+        if rotations is None:
+            rotations = draw_group_rotations(target.shape[0]) if target.dim() == 4 else draw_rotations(4)
+        return ct_hip.acg_u8(target, reference, rotations, nbits=nbits, input_f32=input_f32, out_dtype=out_dtype or torch.float64, out=out)
+    if out_dtype not in (None, torch.float64) or input_f32 is not True or out is not None:
+        raise ValueError("input_f32 / out_dtype / out are for uint8 frames; float frames give a fresh float64 tensor")
     if target.dim() != 3:
         raise ValueError("automated_color_grading_cuda takes one [H,W,3] frame per call")
     graded = iterative_distribution_transfer_cuda(target, reference, rotations=rotations)

@@ -44,6 +44,11 @@ is `host`: PIL on the writer's threads, as before.
 and unfiltered on the GPU (ct_hip.png_decode, csrc/png_decode.hip), N samples' files per call (default 16,
 utils.data.prefetch_decoded); what the device decoder does not take (anything but 8-bit RGB without interlace) is decoded by PIL as
 before, file by file.  Under CT_CLI_DEVICE=cpu it is refused before the first frame.  The default is `host`: nothing changes.
+
+`--model.byte_groups true`, `--model.iterative_groups true`, `--model.grading_groups true` (test, predict; `Runner` with
+`--model.metrics psnr` on a loader of uint8 groups): MK and Xiao, the iterative distribution transfer, automated colour grading take a
+whole group of uint8 frames per call (`Runner.takes_groups()`, `test_group`, `predict_group`) instead of one float32 frame.  Each flag
+touches its own methods only; without them nothing changes.
 """
 import importlib
 import inspect
@@ -444,7 +449,7 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
                     # uint8 frames in pinned groups: one upload, ONE transfer call, one pack and ONE download per group of k frames
                     for n, (ids, dev) in enumerate(prefetch_groups(frames, indices, device)):
                         frames_out = model.predict_group(dev)
-                        if frames_out.dtype == torch.uint8:     # --model.byte_groups: bytes already, freshly allocated (as views are)
+                        if frames_out.dtype == torch.uint8:     # --model.byte_groups / iterative_groups / grading_groups: bytes already, freshly allocated (as views are)
                             writer.submit(ids, frames_out)
                             continue
                         slot, u8 = pack(n, frames_out, "hwc")

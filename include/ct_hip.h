@@ -227,11 +227,47 @@ int ct_mk_u8(const uint8_t *target, const uint8_t *reference, const uint8_t *gt,
  * must not alias the inputs.  Multigrid as in the reference: both images are halved with skimage.transform.resize
  * semantics (Gaussian anti-aliasing sigma (factor-1)/2 with 'mirror' boundary, then bilinear sampling with 'reflect'
  * boundary; scikit-image 0.18.3) while (h+1)/2 > 20 and (w+1)/2 > 20 and nbits has entries left; on every level nbits[level]
- * Jacobi sweeps of iterative.py:106-115.  nbits: HOST array, the reference's default is {4, 16, 32, 64, 64, 64}.
+ * Jacobi sweeps of iterative.py:106-115.  nbits: HOST array, the reference's default is {4, 16, 32, 64, 64, 64}.  The batch-1
+ * call of the code behind ct_regrain_u8.
  * ws: ct_regrain_workspace_bytes(height, width) (16-byte aligned).                                                     */
 size_t ct_regrain_workspace_bytes(int height, int width);
 int ct_regrain_f64(const double *img_in, const double *img_col, double *out, int height, int width, const int *nbits,
                    int n_nbits, void *ws, size_t ws_bytes, void *stream);
+
+/* ct_regrain_u8: the same regrain for `batch` frames of one size in the launches of one frame (every kernel has a frame axis), with
+ * the original target as bytes: img_in uint8 [batch][height][width][3], img_col float64 of that shape.  Byte k stands for
+ * (double)((float)k / 255.0f) (input_f32 = 1) or k / 255.0 (input_f32 = 0), looked up in ct_idt_u8's 256-entry table by the
+ * kernels that read level 0's img_in (weights, level-0 sweeps, first down-resize); everything after the lookup is ct_regrain_f64's
+ * float64 statements, so the float64 result is bitwise ct_regrain_f64 on that image, frame by frame.
+ * Outputs, any non-empty subset (NULL = not wanted), written by the last level-0 launch: out_f64; out_f32 = that value rounded
+ * once; out_u8 = ct_pack_u8_f32's rule on the float32 value (rint(clamp(x, 0, 1) * 255), ties to even, NaN -> 0).  Without
+ * out_f64 no float64 image is stored.  With gt (uint8, the target's shape) psnr_out[batch][2] = (mse, PSNR) of the float32 result
+ * clamped to [0, 1] against (float)k / 255.0f, in float64, one partial per workgroup of that last launch added in a fixed order
+ * by one more launch; nothing is read back.  nbits[0] == 0 still writes every output.
+ * n_nbits outside 1..8, a negative nbits entry, all outputs NULL, gt without psnr_out: CT_E_BADARG; img_col / out_f64 / out_f32 /
+ * psnr_out off their element size: CT_E_ALIGN; ws missing, not 16-byte aligned or smaller than
+ * ct_regrain_u8_workspace_bytes(batch, height, width, n_nbits): CT_E_WORKSPACE -- all before anything touches the device.
+ * Workspace per frame, in doubles: 6 H W (resize scratch) + 8 H W (level 0: two iterates, weights) + 14 h w per further level
+ * + one per workgroup of the last launch.  ct_regrain_u8_workspace_bytes is 0 for refused arguments (batch outside 1..65535,
+ * height * width >= 2^31).  Added under ABI 9.                                                                              */
+size_t ct_regrain_u8_workspace_bytes(int batch, int height, int width, int n_nbits);
+int ct_regrain_u8(const uint8_t *img_in, const double *img_col, int batch, int height, int width, int input_f32,
+                  const int *nbits, int n_nbits, double *out_f64, float *out_f32, uint8_t *out_u8, const uint8_t *gt,
+                  double *psnr_out, void *ws, size_t ws_bytes, void *stream);
+
+/* ct_acg_u8: methods.iterative.automated_color_grading (methods/iterative.py:118-138) for `batch` pairs of uint8 frames: ct_idt_u8
+ * on the bytes (target [batch][height][width][3], reference [batch][n_r][3], rot / rinv [batch][n_iter][9], round_dr_f32 =
+ * input_f32) with its float64 result left in the workspace, then ct_regrain_u8 with the target bytes as img_in and that result as
+ * img_col.  Outputs, gt / psnr_out and nbits as for ct_regrain_u8.  The float64 result is bitwise ct_regrain_f64(image of the
+ * target bytes, ct_idt_u8's float64 output) frame by frame.
+ * Errors before anything touches the device, by ct_idt_u8's rules: n_iter < 1, bins outside 1..1024, n_nbits outside 1..8, all
+ * outputs NULL, gt without psnr_out: CT_E_BADARG; CT_E_ALIGN and CT_E_WORKSPACE as above, against
+ * ct_acg_u8_workspace_bytes = ct_idt_u8_workspace_bytes(batch, n_iter, bins, H W, 0) + 24 H W batch + ct_regrain_u8_workspace_bytes,
+ * each rounded up to 16 (0 for refused arguments).  Added under ABI 9.                                                     */
+size_t ct_acg_u8_workspace_bytes(int batch, int height, int width, int n_iter, int bins, int n_nbits);
+int ct_acg_u8(const uint8_t *target, const uint8_t *reference, int64_t n_r, const uint8_t *gt, int batch, int height, int width,
+              const double *rot, const double *rinv, int n_iter, int bins, int input_f32, const int *nbits, int n_nbits,
+              double *out_f64, float *out_f32, uint8_t *out_u8, double *psnr_out, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- test-set distortions (utils/data.py:12-22,120-125): torchvision.transforms.functional.adjust_* on a uint8 frame ----
  * in: uint8 [3][height][width] (what read_image returns).  kind: 0 identity, 1 brightness, 2 contrast, 3 saturation

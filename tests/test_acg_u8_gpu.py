@@ -1,0 +1,390 @@
+"""Automated colour grading on uint8 frame groups (ct_regrain_u8, ct_acg_u8; ct_hip.regrain_u8, ct_hip.acg_u8) on the GPU, and its
+route through methods.iterative, Runner(grading_groups=True) and `utils.cli --model.grading_groups true`.
+
+Bounds, none of them taken from the code under test:
+  float64 out   bitwise ct_hip.regrain (ct_regrain_f64, one frame per call) on the image the bytes stand for -- float32(k) /
+                float32(255) (input_f32) or k / 255.0 -- and on ct_hip.idt_u8's float64 result: the byte kernels run the float64
+                kernels' statements after a table lookup, the batched kernels those of one frame
+  float32 out   bitwise `.float()` of the float64 output (one rounding); bytes bitwise ct_hip.pack_u8 of that
+  mse           3 N 2^-53 relative to numpy's float64 mean of the squared differences of the entry's own float32 output (clamped)
+                and float32(gt) / float32(255), N pixels: what the IDT twin of this file allows (other partial sums, same terms)
+  oracle        1e-11 against oracle.regrain.regrain: what tests/test_regrain.py asserts for ct_regrain_f64 at all its sizes
+"""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import iterative as oit
+from oracle import regrain as org
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG = os.path.join(ROOT, "color-transfer_amd", "configs")
+ACG_SPEC = "methods.iterative.automated_color_grading"
+ULP = 2.0 ** -53
+KINDS = (torch.float64, torch.float32, torch.uint8)
+
+
+def dev(a):
+    return torch.from_numpy(np.array(a, copy=True)).cuda()
+
+
+def scene(h, w, batch, seed):
+    """seeded bytes [batch, h, w, 3] with smooth structure plus noise (tests/test_regrain.py's image, quantised); every frame differs"""
+    rng = np.random.default_rng(7919 * seed + 31 * h + w)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    out = []
+    for b in range(batch):
+        i = np.stack([0.5 + 0.4 * np.sin(xx / (15.0 + b)), 0.2 + 0.6 * yy / h, 0.5 + 0.4 * np.cos((xx + yy) / (23.0 - 2 * b))], -1)
+        out.append(np.rint(np.clip(i + 0.03 * rng.standard_normal((h, w, 3)), 0, 1) * 255).astype(np.uint8))
+    return np.stack(out)
+
+
+def graded(k, seed):
+    """a float64 image like an IDT result of the frames k: unclipped, near the frames"""
+    rng = np.random.default_rng(seed)
+    return (k / 255.0) ** 0.9 * 0.95 + 0.03 * rng.standard_normal(k.shape)
+
+
+def rotations(n_iter, seed, batch=None):
+    np.random.seed(seed)
+    return oit.draw_rotations(n_iter) if batch is None else np.stack([oit.draw_rotations(n_iter) for _ in range(batch)])
+
+
+def image(k, f32):
+    """the float image the bytes stand for"""
+    return k.astype(np.float32) / np.float32(255) if f32 else k / 255.0
+
+
+def bits(t):
+    """an integer view: equal bits, a NaN for the same NaN"""
+    return t.view({torch.float64: torch.int64, torch.float32: torch.int32}.get(t.dtype, t.dtype))
+
+
+def same(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and bool(torch.equal(bits(a), bits(b)))
+
+
+def composition(t, r, rot, f32, nbits=None):
+    """the public calls one after the other, frame by frame: ct_hip.regrain(image of the target, ct_hip.idt_u8 float64)"""
+    import ct_hip
+    col = ct_hip.idt_u8(dev(t), dev(r), rot, input_f32=f32, out_dtype=torch.float64)
+    kw = {} if nbits is None else {"nbits": nbits}
+    return torch.stack([ct_hip.regrain(dev(image(t[b], f32)), col[b], **kw) for b in range(t.shape[0])])
+
+
+# ---------------------------------------------------------------------------------------------------- 1. the regrain alone
+# (40, 45), (21, 300): the recursion stops at once; (5, 7): edge clamping everywhere, the region smaller than a tile; (83, 171): three
+# levels, odd sizes at every level; (420, 500): above the 200 000-pixel switch to 16 x 32 tiles
+SHAPES = ((40, 45), (21, 300), (5, 7), (83, 171), (420, 500))
+
+
+@pytest.mark.parametrize("f32", (True, False))
+@pytest.mark.parametrize("shape", SHAPES)
+def test_regrain_alone_bitwise(shape, f32):
+    import ct_hip
+    h, w = shape
+    t = scene(h, w, 3, 1)
+    col = dev(graded(t, h + w))
+    out = ct_hip.regrain_u8(dev(t), col, input_f32=f32)
+    assert out.dtype == torch.float64 and tuple(out.shape) == t.shape
+    for b in range(3):
+        assert same(out[b], ct_hip.regrain(dev(image(t[b], f32)), col[b])), b
+
+
+# a sweep count below the block of 8 on both levels; no sweep on level 0; the single-sweep kernel as the last launch and as a
+# remainder (9 = 8 + 1); one level only
+@pytest.mark.parametrize("nbits", ((4,), (3, 5), (0, 4), (1, 9), (9, 1), (0,)))
+def test_regrain_alone_nbits(nbits):
+    import ct_hip
+    t = scene(83, 171, 3, 2)
+    col, g = dev(graded(t, 5)), dev(scene(83, 171, 3, 3))
+    (o64, o32, o8), ps = ct_hip.regrain_u8(dev(t), col, nbits=nbits, out=[torch.empty(t.shape, dtype=dt, device="cuda") for dt in KINDS], gt=g)
+    for b in range(3):
+        assert same(o64[b], ct_hip.regrain(dev(image(t[b], True)), col[b], nbits=nbits)), b
+    assert same(o32, o64.float()) and same(o8, ct_hip.pack_u8(o32, "hwc"))
+    assert bool(torch.isfinite(ps).all())
+
+
+# ---------------------------------------------------------------------------------------------------- 2. the whole method
+@pytest.mark.parametrize("f32", (True, False))
+@pytest.mark.parametrize("shape,ref_shape", (((83, 171), (83, 171)), ((40, 45), (30, 50))))
+def test_whole_method_bitwise(shape, ref_shape, f32):
+    import ct_hip
+    import methods.iterative as it
+    t, r, rot = scene(*shape, 3, 4), scene(*ref_shape, 3, 5), rotations(4, 11, 3)
+    out = ct_hip.acg_u8(dev(t), dev(r), rot, input_f32=f32, out_dtype=torch.float64)
+    assert out.dtype == torch.float64 and tuple(out.shape) == t.shape
+    assert same(out, composition(t, r, rot, f32))
+    if f32:                                                            # the per-frame route a Runner takes today
+        for b in range(3):
+            assert same(out[b], it.automated_color_grading_cuda(dev(image(t[b], True)), dev(image(r[b], True)), rotations=rot[b])), b
+        # and the methods entry on the bytes
+        assert same(it.automated_color_grading_cuda(dev(t), dev(r), rotations=rot), out)
+        assert same(it.automated_color_grading_cuda(dev(t), dev(r), rotations=rot, out_dtype=torch.uint8), ct_hip.acg_u8(dev(t), dev(r), rot))
+        np.random.seed(5)
+        drawn = it.automated_color_grading_cuda(dev(t), dev(r), out_dtype=torch.float32)
+        np.random.seed(5)
+        assert same(drawn, ct_hip.acg_u8(dev(t), dev(r), it.draw_group_rotations(3), out_dtype=torch.float32))
+        with pytest.raises(ValueError):                                # float frames: one frame per call, as before
+            it.automated_color_grading_cuda(dev(image(t, True)), dev(image(r, True)), rotations=rot)
+
+
+# ---------------------------------------------------------------------------------------------------- 3. outputs and metric
+@pytest.mark.parametrize("shape", ((83, 171), (40, 45)))
+def test_outputs_and_metric(shape):
+    import ct_hip
+    h, w = shape
+    n = h * w
+    tk, rk, gk, rot = scene(h, w, 3, 6), scene(h, w, 3, 7), scene(h, w, 3, 8), rotations(4, 21, 3)
+    t, r, g = dev(tk), dev(rk), dev(gk)
+    o64 = ct_hip.acg_u8(t, r, rot, out_dtype=torch.float64)
+    o32 = ct_hip.acg_u8(t, r, rot, out_dtype=torch.float32)
+    o8 = ct_hip.acg_u8(t, r, rot)                                      # bytes by default: no float64 image is stored
+    assert o64.dtype == torch.float64 and o32.dtype == torch.float32 and o8.dtype == torch.uint8
+    assert same(o32, o64.float()) and same(o8, ct_hip.pack_u8(o32, "hwc"))
+    want = dict(zip(KINDS, (o64, o32, o8)))
+    psnr = None
+    for mask in range(1, 8):                                           # every combination of the three outputs, with the metric
+        outs = [torch.empty(t.shape, dtype=dt, device="cuda") for i, dt in enumerate(KINDS) if mask >> i & 1]
+        got, ps = ct_hip.acg_u8(t, r, rot, out=outs, gt=g)
+        assert all(same(o, want[o.dtype]) for o in got), mask
+        psnr = ps if psnr is None else psnr
+        assert same(ps, psnr), mask                                    # two runs are bitwise equal, the partials' sum included
+    mine = torch.empty_like(o8)
+    assert ct_hip.acg_u8(t, r, rot, out=mine).data_ptr() == mine.data_ptr() and same(mine, o8)
+    assert psnr.dtype == torch.float64 and tuple(psnr.shape) == (3, 2)
+    o, ps = o32.cpu().numpy(), psnr.cpu().numpy()
+    for b in range(3):
+        d = np.clip(o[b], 0, 1).astype(np.float64) - (gk[b].astype(np.float32) / np.float32(255)).astype(np.float64)
+        mse = float(np.mean(d * d))
+        err = abs(ps[b, 0] - mse) / mse
+        print("%dx%d frame %d: mse %.17g, relative error %.3g (bound %.3g)" % (h, w, b, mse, err, 3 * n * ULP))
+        assert err <= 3 * n * ULP
+        assert abs(ps[b, 1] - 10 * np.log10(1 / mse)) <= 1e-12 * max(1.0, abs(ps[b, 1]))
+
+
+# ---------------------------------------------------------------------------------------------------- 4. batch independence
+@pytest.mark.parametrize("shape", ((83, 171), (40, 45)))
+def test_batch_independence(shape):
+    import ct_hip
+    h, w = shape
+    t, r, g, rot = dev(scene(h, w, 3, 9)), dev(scene(h, w, 3, 10)), dev(scene(h, w, 3, 11)), rotations(4, 31, 3)
+
+    def run(a, b, **kw):
+        return ct_hip.acg_u8(t[a:b], r[a:b], rot[a:b], out=[torch.empty((b - a, h, w, 3), dtype=dt, device="cuda") for dt in KINDS], gt=g[a:b], **kw)
+
+    whole, ps = run(0, 3)
+    for b in range(3):
+        one, ps1 = run(b, b + 1)
+        assert all(same(x[0], y[b]) for x, y in zip(one, whole)), b
+        assert same(ps1[0], ps[b]), b                                  # a frame's partials do not depend on its neighbours
+    split, ps2 = run(0, 3, frames_per_call=2)
+    assert all(same(x, y) for x, y in zip(split, whole)) and same(ps2, ps)
+    col = ct_hip.idt_u8(t, r, rot, out_dtype=torch.float64)
+    assert same(ct_hip.regrain_u8(t, col, frames_per_call=1), ct_hip.regrain_u8(t, col))
+
+
+# ---------------------------------------------------------------------------------------------------- 5. oracle anchor
+def test_oracle_anchor():
+    import ct_hip
+    h, w = 83, 171
+    tk, rk, rot = scene(h, w, 2, 12), scene(h, w, 2, 13), rotations(4, 41, 2)
+    out = ct_hip.acg_u8(dev(tk), dev(rk), rot, input_f32=False, out_dtype=torch.float64).cpu().numpy()
+    col = ct_hip.idt_u8(dev(tk), dev(rk), rot, input_f32=False, out_dtype=torch.float64).cpu().numpy()   # held bitwise to its C oracle elsewhere
+    for b in range(2):
+        want = org.regrain(image(tk[b], False), col[b])
+        err = float(np.abs(out[b] - want).max())
+        print("frame %d: max |device - oracle| = %.3g (bound 1e-11)" % (b, err))
+        assert err < 1e-11
+
+
+# ---------------------------------------------------------------------------------------------------- 6. a constant target
+def test_constant_target_frame():
+    import ct_hip
+    h, w = 40, 45
+    tk, rk, rot = scene(h, w, 3, 14), scene(h, w, 3, 15), rotations(4, 51, 3)
+    tk[1] = (200, 30, 101)
+    o64, o32, o8 = ct_hip.acg_u8(dev(tk), dev(rk), rot, out=[torch.empty(tk.shape, dtype=dt, device="cuda") for dt in KINDS])
+    want = composition(tk, rk, rot, True)
+    assert np.array_equal(o64.cpu().numpy(), want.cpu().numpy(), equal_nan=True) and same(o64, want)
+    assert same(o32, want.float()) and same(o8, ct_hip.pack_u8(want.float().contiguous(), "hwc"))
+    nan = torch.isnan(want)
+    assert not bool(o8[nan].any())                                     # bytes for NaN are 0
+
+
+# ---------------------------------------------------------------------------------------------------- 7. refusals
+def test_refusals_launch_nothing():
+    import ct_hip
+    E = ct_hip.CtHipError
+    h, w, B = 40, 45, 3
+    t, r, g, rot = dev(scene(h, w, B, 16)), dev(scene(h, w, B, 17)), dev(scene(h, w, B, 18)), rotations(4, 61)
+    col = torch.zeros(t.shape, dtype=torch.float64, device="cuda")
+    ps_ok = torch.empty((B, 2), dtype=torch.float64, device="cuda")
+    calls = [
+        lambda: ct_hip.acg_u8(t, r, rot, out=[]),                                                         # all outputs missing
+        lambda: ct_hip.acg_u8(t, r, rot, gt=g[:2]), lambda: ct_hip.acg_u8(t, r, rot, gt=g[:, :20].contiguous()),   # gt of another shape
+        lambda: ct_hip.acg_u8(t, r, rot, psnr_out=ps_ok),                                                 # psnr_out without gt
+        lambda: ct_hip.acg_u8(t.float(), r, rot), lambda: ct_hip.acg_u8(t, r.float(), rot),               # float tensors
+        lambda: ct_hip.acg_u8(t.double() / 255, r.double() / 255, rot),
+        lambda: ct_hip.acg_u8(t, r, rot, nbits=()), lambda: ct_hip.acg_u8(t, r, rot, nbits=(4,) * 9),     # nbits of 0 or 9 entries
+        lambda: ct_hip.acg_u8(t, r, rot, nbits=(4, -1)),
+        lambda: ct_hip.acg_u8(t, r, np.stack([rot] * 2)), lambda: ct_hip.acg_u8(t, r, rot[:0]),           # rotations of the wrong batch
+        lambda: ct_hip.acg_u8(t, r[:2], rot), lambda: ct_hip.acg_u8(t, r, rot, bins=0), lambda: ct_hip.acg_u8(t, r, rot, bins=1025),
+        lambda: ct_hip.acg_u8(t, r, rot, out_dtype=torch.float16), lambda: ct_hip.acg_u8(t, r, rot, out=[torch.empty_like(t), torch.empty_like(t)]),
+        lambda: ct_hip.acg_u8(t, r, rot, frames_per_call=0),
+        lambda: ct_hip.regrain_u8(t, col, out=[]), lambda: ct_hip.regrain_u8(t, col[:2]), lambda: ct_hip.regrain_u8(t, col.float()),
+        lambda: ct_hip.regrain_u8(t.float(), col), lambda: ct_hip.regrain_u8(t, col, nbits=()), lambda: ct_hip.regrain_u8(t, col, nbits=(1,) * 9),
+        lambda: ct_hip.regrain_u8(t, col, psnr_out=ps_ok), lambda: ct_hip.regrain_u8(t, col, gt=g[:2]),
+    ]
+    for i, call in enumerate(calls):
+        with pytest.raises(E) as info:
+            call()
+            pytest.fail("call %d raised nothing" % i)
+        assert str(info.value)
+    for call, name in ((calls[3], "psnr_out"), (calls[4], "target"), (calls[5], "reference"), (calls[7], "nbits"), (calls[10], "rotations"),
+                       (calls[1], "gt"), (calls[0], "out")):
+        with pytest.raises(E, match=name):                            # the message names the argument
+            call()
+    # the C entries answer for themselves too, before anything touches the device
+    lib, null = ct_hip.lib(), None
+    rot_b = np.broadcast_to(rot, (B, 4, 3, 3))
+    both = dev(np.stack([rot_b, np.linalg.inv(rot_b)]).reshape(2, B, 4, 9))
+    import ctypes
+    nb = (ctypes.c_int * 9)(4, 16, 32, 64, 64, 64, 64, 64, 64)
+    nbp = ctypes.cast(nb, ctypes.c_void_p)
+    out, o64 = torch.empty_like(t), torch.empty(t.shape, dtype=torch.float64, device="cuda")
+    ps = torch.empty((B, 2), dtype=torch.float64, device="cuda")
+    need = lib.ct_acg_u8_workspace_bytes(B, h, w, 4, 255, 6)
+    ws = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+
+    def entry(gt=null, n_iter=4, bins=255, n_nbits=6, f64=null, f32=null, u8=null, psnr=null, wsp=ws.data_ptr(), wsb=need):
+        return lib.ct_acg_u8(t.data_ptr(), r.data_ptr(), h * w, gt, B, h, w, both[0].data_ptr(), both[1].data_ptr(), n_iter, bins, 1, nbp, n_nbits,
+                             f64, f32, u8, psnr, wsp, wsb, null)
+
+    assert entry() == -1                                                           # all three outputs absent
+    assert entry(u8=out.data_ptr(), gt=g.data_ptr()) == -1                         # gt without psnr_out
+    assert entry(u8=out.data_ptr(), n_nbits=0) == -1 and entry(u8=out.data_ptr(), n_nbits=9) == -1
+    assert entry(u8=out.data_ptr(), n_iter=0) == -1 and entry(u8=out.data_ptr(), bins=1025) == -1
+    assert entry(u8=out.data_ptr(), wsb=need - 1) == -2                            # a workspace one byte short
+    assert entry(u8=out.data_ptr(), wsp=null) == -2 and entry(u8=out.data_ptr(), wsp=ws.data_ptr() + 8) == -2
+    assert entry(f64=o64.data_ptr() + 4) == -3 and entry(f32=o64.data_ptr() + 2) == -3
+    need_rg = lib.ct_regrain_u8_workspace_bytes(B, h, w, 6)
+
+    def regrain_entry(u8=null, gt=null, psnr=null, n_nbits=6, wsb=need_rg):
+        return lib.ct_regrain_u8(t.data_ptr(), col.data_ptr(), B, h, w, 1, nbp, n_nbits, null, null, u8, gt, psnr, ws.data_ptr(), wsb, null)
+
+    assert regrain_entry() == -1 and regrain_entry(u8=out.data_ptr(), gt=g.data_ptr()) == -1 and regrain_entry(u8=out.data_ptr(), n_nbits=9) == -1
+    assert regrain_entry(u8=out.data_ptr(), wsb=need_rg - 1) == -2
+    out.zero_()
+    assert entry(u8=out.data_ptr(), f64=o64.data_ptr(), gt=g.data_ptr(), psnr=ps.data_ptr()) == 0
+    torch.cuda.synchronize()
+    assert same(out, ct_hip.acg_u8(t, r, rot))
+
+
+# ---------------------------------------------------------------------------------------------------- 8. Runner and CLI
+H, W, FRAMES, GROUP = 24, 40, 5, 3               # the IDT twin's loader: two groups, the second one ragged
+
+
+def grouped_frames(video):
+    """the frames as the grouped route sees them (a group's content is defined by its first frame): [(target, reference, gt)] uint8 HWC"""
+    out = []
+    for first in range(0, FRAMES, video.group):
+        chunk = video.host_chunk(first)
+        out += [tuple(chunk[i, j] for i in range(3)) for j in range(min(video.group, FRAMES - first))]
+    return out
+
+
+def per_frame_route(triples, seed):
+    """the per-frame Runner (forward, clamp, pack_u8; test_step) on a seeded np.random, for uint8 HWC (target, reference, gt) triples
+    made float32 CHW as the datasets make them: (bytes [n,H,W,3], rows [n,2] of (mse, PSNR) as methods.psnr computes them)"""
+    import ct_hip
+    from methods import Runner
+    model = Runner(ACG_SPEC, metrics="psnr")
+    assert not model.takes_groups()
+    batches = [{k: (x.permute(2, 0, 1).float() / 255)[None].cuda() for k, x in zip(("target", "reference", "gt"), tr)} for tr in triples]
+    np.random.seed(seed)
+    frames_u8 = [ct_hip.pack_u8(model(b).clamp(0, 1).contiguous(), "chw")[0].cpu().numpy() for b in batches]
+    np.random.seed(seed)
+    rows = [ct_hip.frame_psnr(model(b).clamp(0, 1).float().contiguous(), b["gt"].float().contiguous())[0].cpu().numpy() for b in batches]
+    return np.stack(frames_u8), np.stack(rows)
+
+
+def psnr_close(got, want, n):
+    """PSNR values of mse values that agree within 3 n 2^-53 relative: d(10 log10(1 / mse)) = 10 / ln 10 * d(mse) / mse, plus the
+    1e-12 relative that test_mk_psnr allows for the logarithm itself"""
+    got, want = np.asarray(got), np.asarray(want)
+    return bool((np.abs(got - want) <= 10 / np.log(10) * 3 * n * ULP + 1e-12 * np.maximum(1.0, np.abs(want))).all())
+
+
+def test_runner_groups():
+    from methods import Runner
+    from utils.data import SyntheticStereoVideoU8, prefetch_groups
+    video = SyntheticStereoVideoU8(FRAMES, H, W, group=FRAMES, pool=2)
+    want8, want_psnr = per_frame_route(grouped_frames(video), 77)
+    model = Runner(ACG_SPEC, metrics="psnr", grading_groups=True)
+    assert model.takes_groups() and not Runner(ACG_SPEC, metrics="psnr", iterative_groups=True).takes_groups()
+    device = torch.device("cuda", torch.cuda.current_device())
+    rec = torch.zeros((FRAMES, 2), dtype=torch.float64, device=device)
+    (ids, group), = list(prefetch_groups(video, range(FRAMES), device))
+    assert len(ids) == FRAMES
+    np.random.seed(77)
+    got8 = model.predict_group(group)
+    assert got8.dtype == torch.uint8 and tuple(got8.shape) == (FRAMES, H, W, 3)
+    assert np.array_equal(got8.cpu().numpy(), want8)
+    assert model.predict_group(group).data_ptr() != got8.data_ptr()                 # freshly allocated frames
+    np.random.seed(77)
+    out = model.test_group(group, rec)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (FRAMES, H, W, 3)
+    got = rec.cpu().numpy()
+    for f in range(FRAMES):
+        err = abs(got[f, 0] - want_psnr[f, 0]) / want_psnr[f, 0]
+        print("frame %d: mse %.17g, relative difference %.3g (bound %.3g)" % (f, got[f, 0], err, 3 * H * W * ULP))
+        assert err <= 3 * H * W * ULP
+    assert psnr_close(got[:, 1], want_psnr[:, 1], H * W)
+
+
+# one fresh process runs `test` and `predict --format npy` with and without the flag, each seeded: with one frame per group both
+# routes see the same frames, with GROUP frames per group the grouped route sees grouped_frames()
+CHILD = r"""
+import json, sys
+sys.path[:0] = json.loads(sys.argv[1])
+import numpy as np
+from utils import cli
+base, out = json.loads(sys.argv[2]), sys.argv[3]
+for tag, extra in (("plain1", ["--data.group", "1"]), ("groups1", ["--data.group", "1", "--model.grading_groups", "true"]),
+                   ("groups3", ["--data.group", "3", "--model.grading_groups", "true"])):
+    np.random.seed(123)
+    assert cli.main(["predict"] + base + extra + ["--format", "npy", "--output", out + "/" + tag], timing=None) == 5
+    np.random.seed(321)
+    np.save(out + "/" + tag + ".test.npy", cli.main(["test"] + base + extra).cpu().numpy())
+"""
+
+
+def test_cli_grading_groups(tmp_path):
+    from utils.data import SyntheticStereoVideoU8
+    base = ["--config", os.path.join(CFG, "others.yaml"), "--model.func_spec", ACG_SPEC, "--model.metrics", "psnr", "--data.data_dir", "null",
+            "--data.synthetic", "video_u8", "--data.n_frames", str(FRAMES), "--data.height", str(H), "--data.width", str(W)]
+    done = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", CHILD, json.dumps([p for p in sys.path if p]), json.dumps(base), str(tmp_path)],
+                          capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert done.returncode == 0, done.stdout[-2000:] + done.stderr[-4000:]
+    plain, groups1, groups3 = (np.load(tmp_path / (tag + ".test.npy")) for tag in ("plain1", "groups1", "groups3"))
+    assert plain.shape == groups1.shape == groups3.shape == (FRAMES, 4)
+    # the same metrics and the same bytes as without the flag
+    assert psnr_close(groups1[:, 0], plain[:, 0], H * W) and np.isnan(groups1[:, 1:]).all() and not np.isnan(plain[:, 0]).any()
+    for f in range(FRAMES):
+        a, b = np.load(tmp_path / "plain1" / ("%06d.npy" % f)), np.load(tmp_path / "groups1" / ("%06d.npy" % f))
+        assert a.dtype == np.uint8 and a.shape == (H, W, 3) and np.array_equal(a, b), f
+    # whole groups, the second one ragged: the per-frame route on the frames the groups hold
+    video = SyntheticStereoVideoU8(FRAMES, H, W, group=GROUP)
+    want8, _ = per_frame_route(grouped_frames(video), 123)
+    _, want_psnr = per_frame_route(grouped_frames(video), 321)
+    assert psnr_close(groups3[:, 0], want_psnr[:, 1], H * W)
+    for f in range(FRAMES):
+        assert np.array_equal(np.load(tmp_path / "groups3" / ("%06d.npy" % f)), want8[f]), f
