@@ -1,4 +1,5 @@
-// ct_bytes.h -- uint8 frames in 16-byte loads, for every kernel that reads interleaved RGB bytes (linear_u8.hip, idt.hip).
+// ct_bytes.h -- uint8 frames in 16-byte loads, for every kernel that reads interleaved RGB bytes (linear_u8.hip, idt.hip), and
+// the float64 image that the bytes stand for (idt.hip, regrain.hip).
 // Frame b of a batch starts at b * 3 * n_pixels bytes, off the 16-byte grid for most sizes: a frame is its first h < 16 pixels
 // (3 h = -base mod 16), runs of 16 pixels = 48 bytes = three 16-byte loads, and a tail of < 16 pixels.
 // Device inline functions only.
@@ -30,6 +31,26 @@ __device__ __forceinline__ void load48(const uint8_t *p, unsigned int (&w)[12]) 
 __device__ __forceinline__ void load48_bytes(const uint8_t *p, unsigned int (&w)[12]) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) w[i] = pack4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]);
+}
+
+// ---- the image behind the bytes ----------------------------------------------------------------------------------------------
+// The bytes of a frame stand for one of two float64 images, chosen per call: entry k of a 256-entry table in LDS is
+// (double)((float)k / 255.0f) (input_f32: the float32 tensor a Runner makes of a frame) or (double)k / 255.0 (img_as_float).  A
+// kernel instantiated for uint8_t runs the float kernel's statements on the table's values: bitwise the float entry on that image.
+template <typename T> struct IsU8 { static constexpr bool v = false; };
+template <> struct IsU8<uint8_t> { static constexpr bool v = true; };
+
+// by the first 256 threads of the workgroup (all256: the workgroup has no others, no guard is compiled); the caller's next
+// barrier publishes it
+__device__ __forceinline__ void fill_u8_table(double *tab, int input_f32, bool all256 = false) {
+    const unsigned int k = all256 ? threadIdx.x & 255 : threadIdx.x;
+    if (all256 || k < 256) tab[k] = input_f32 ? (double)((float)k / 255.0f) : (double)k / 255.0;
+}
+
+// element e of an image of T as float64
+template <typename T> __device__ __forceinline__ double ld_u8(const T *p, size_t e, const double *tab) {
+    if constexpr (IsU8<T>::v) return tab[p[e]];
+    else return p[e];
 }
 
 }  // namespace ct

@@ -18,13 +18,15 @@
 // Hence bin indices, counts, LUTs AND the float64 output are bitwise identical to the oracle.
 //
 // ct_idt_u8 (uint8 frames in; float64, float32 and / or bytes out, + PSNR) runs the same kernels instantiated for uint8_t: a byte
-// is looked up in a 256-entry float64 table (which of two images it stands for: idt_fill_table) and then takes the statements
+// is looked up in the 256-entry float64 table of the image it stands for (ct_bytes.h: fill_u8_table) and then takes the statements
 // above, so the byte entry is bitwise the float entry on that image.  Its last apply sweep (idt_apply_kernel<., true>) writes the
-// requested outputs and the squared-error partials of the metric instead of (or besides) the float64 working image.
+// requested outputs and the squared-error partials of the metric (ct_u8_frames.h: U8Sinks) instead of (or besides) the float64
+// working image.
 #include "ct_bytes.h"
 #include "ct_common.h"
 #include "ct_metrics.h"
 #include "ct_quant.h"
+#include "ct_u8_frames.h"
 
 namespace ct {
 
@@ -44,18 +46,6 @@ __device__ __forceinline__ double key_f64(unsigned long long k) {
 
 __device__ __forceinline__ double proj(const double *r, double x0, double x1, double x2) {
     return fma(r[2], x2, fma(r[1], x1, r[0] * x0));
-}
-
-// ---- uint8 frames (ct_idt_u8) ----------------------------------------------------------------------------------------------
-// The bytes stand for one of two float64 images, chosen per call: entry k of a 256-entry table in LDS is
-// (double)((float)k / 255.0f) (input_f32: the float32 tensor the Runner makes of a frame) or (double)k / 255.0 (img_as_float).
-// Every sweep below is the float sweep's statements on that table's values, so the byte entry is bitwise the float entry.
-template <typename T> struct IsU8 { static constexpr bool v = false; };
-template <> struct IsU8<uint8_t> { static constexpr bool v = true; };
-
-// by the first 256 threads of the workgroup; the caller's next barrier publishes it
-__device__ __forceinline__ void idt_fill_table(double *tab, int input_f32) {
-    if (threadIdx.x < 256) tab[threadIdx.x] = input_f32 ? (double)((float)threadIdx.x / 255.0f) : (double)threadIdx.x / 255.0;
 }
 
 // fn(i, x0, x1, x2) for the pixels of one image that this thread takes in a grid of NT-thread workgroups.  Float images: one
@@ -144,7 +134,7 @@ __global__ __launch_bounds__(kIdtBlock) void idt_minmax_kernel(const T *__restri
     __shared__ unsigned long long lds[4 * 6 * RG];
     __shared__ double tab[U8 ? 256 : 1];
     if constexpr (U8) {
-        idt_fill_table(tab, input_f32);
+        fill_u8_table(tab, input_f32);
         __syncthreads();
     }
     const int b = blockIdx.y;
@@ -314,7 +304,7 @@ __global__ __launch_bounds__(kIdtHistBlock) void idt_hist_kernel(const TT *__res
     extern __shared__ unsigned int lh[];  // [2][3][bins]
     __shared__ unsigned long long kstage[kMmShards * 12], keys[12];
     __shared__ double tab[(IsU8<TT>::v || IsU8<TR>::v) ? 256 : 1];
-    if constexpr (IsU8<TT>::v || IsU8<TR>::v) idt_fill_table(tab, input_f32);   // published by the barriers of idt_reduce_keys
+    if constexpr (IsU8<TT>::v || IsU8<TR>::v) fill_u8_table(tab, input_f32);   // published by the barriers of idt_reduce_keys
     const int b = blockIdx.y;
     for (int i = threadIdx.x; i < 6 * bins; i += kIdtHistBlock) lh[i] = 0;
     double r[9], lo[3], hi[3], step[3], scale[3];
@@ -457,16 +447,6 @@ __global__ __launch_bounds__(kIdtBlock) void idt_lut_kernel(const unsigned int *
 // A9 (+ next iteration's A6): d_r = interp(d0r, edges[1:], f, left=0); t += rinv @ (d_r - d0r)
 // grid = (G, batch); dynamic LDS = 3*bins*16 B
 // -------------------------------------------------------------------------------------------
-// What the LAST apply sweep of ct_idt_u8 writes besides (or instead of) the float64 image: the result rounded once to float32,
-// its bytes by ct_quant.h's rule, and per workgroup one float64 partial sum of (clamp(float32 result, 0, 1) - gt)^2, gt as
-// float32 k / 255 (IEEE division), added per thread in pixel order and then by block_sum's fixed tree.
-struct IdtSinks {
-    float *f32;          // [batch][n_t][3] or NULL
-    uint8_t *u8;         // [batch][n_t][3] or NULL
-    const uint8_t *gt;   // [batch][n_t][3] or NULL
-    double *sq;          // [batch][kMaxBlocksPerImage], written when gt is given
-};
-
 constexpr int kIdtTilePx = 256;                  // pixels of one wave's tile: 768 bytes = 48 16-byte vectors
 constexpr int kIdtTileBytes = 3 * kIdtTilePx;
 
@@ -482,13 +462,14 @@ __device__ __forceinline__ void idt_wave_sync() {
 // target bytes (and ground-truth bytes) come in as 16-byte loads into the wave's LDS buffer, lane l then owns pixels l, l + 64,
 // l + 128, l + 192 of the tile -- so the float64 and float32 stores of a wave are contiguous, never a long run per lane -- and
 // the result bytes go back through the same buffer and out as 16-byte stores.  The pixels in front of the first tile and behind
-// the last take the same arithmetic one by one in workgroup 0.  LAST stores the float64 image only when `out` is given.
+// the last take the same arithmetic one by one in workgroup 0.  LAST writes sk (ct_u8_frames.h; partials [batch][kMaxBlocksPerImage])
+// except sk.f64: the float64 image goes to `out`, and only when that is given.
 template <typename TT, bool LAST>
 __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restrict__ tgt, double *__restrict__ out, int64_t n_t,
                                                               const double *__restrict__ rot, const double *__restrict__ rinv,
                                                               const double *__restrict__ lut,
                                                               int n_iter, int it, int bins, int round_f32,
-                                                              unsigned long long *__restrict__ mm, int input_f32, IdtSinks sk) {
+                                                              unsigned long long *__restrict__ mm, int input_f32, U8Sinks sk) {
     constexpr bool U8 = IsU8<TT>::v;
     constexpr bool TILED = U8 || LAST;
     extern __shared__ double2 sl[];  // [3][bins] (f, slope)
@@ -504,7 +485,7 @@ __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restri
         const double2 *g = reinterpret_cast<const double2 *>(lut + ((size_t)b * n_iter + it) * 3 * bins * 2);
         for (int i = threadIdx.x; i < 3 * bins; i += kIdtBlock) sl[i] = g[i];
     }
-    if constexpr (U8) idt_fill_table(tab, input_f32);                       // published by the barriers of idt_reduce_keys
+    if constexpr (U8) fill_u8_table(tab, input_f32);                       // published by the barriers of idt_reduce_keys
     if constexpr (LAST) tabf[threadIdx.x] = (float)threadIdx.x / 255.0f;    // kIdtBlock == 256: one entry per thread
     double r[9], ri[9], rn[9], lo[3], hi[3], step[3], scale[3];
     const bool has_next = !LAST && (it + 1 < n_iter);
@@ -572,11 +553,7 @@ __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restri
         uint8_t *o8 = (LAST && sk.u8) ? sk.u8 + off : nullptr;
         const uint8_t *g = (LAST && sk.gt) ? sk.gt + off : nullptr;
         double acc[1] = {0.0};
-        auto sqerr = [&](float v, unsigned int kgt) {
-            const float c = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
-            const double d = (double)c - (double)tabf[kgt];
-            acc[0] += d * d;
-        };
+        auto sqerr = [&](float v, unsigned int kgt) { acc[0] += sq_err(v, [&] { return tabf[kgt]; }); };
         // the tiles start on the 16-byte grid of a buffer whose base is aligned; a buffer that is not takes byte accesses
         const int h = head_pixels((uintptr_t)off, n_t);
         const int64_t n_tiles = (n_t - h) / kIdtTilePx;
@@ -639,10 +616,8 @@ __global__ __launch_bounds__(kIdtBlock) void idt_apply_kernel(const TT *__restri
             const int64_t done = h + n_tiles * kIdtTilePx, n_rest = h + (n_t - done);   // < 16 + 256 + 16
             for (int64_t rr = threadIdx.x; rr < n_rest; rr += kIdtBlock) {
                 const int64_t i = rr < h ? rr : done + (rr - h);
-                double x0, x1, x2, y0, y1, y2;
-                if constexpr (U8) { x0 = tab[p[3 * i]]; x1 = tab[p[3 * i + 1]]; x2 = tab[p[3 * i + 2]]; }
-                else { x0 = (double)p[3 * i]; x1 = (double)p[3 * i + 1]; x2 = (double)p[3 * i + 2]; }
-                pixel(i, x0, x1, x2, y0, y1, y2);
+                double y0, y1, y2;
+                pixel(i, ld_u8(p, 3 * i, tab), ld_u8(p, 3 * i + 1, tab), ld_u8(p, 3 * i + 2, tab), y0, y1, y2);
                 if constexpr (LAST) {
                     const float v[3] = {(float)y0, (float)y1, (float)y2};
 #pragma unroll
@@ -724,8 +699,7 @@ static int idt_apply_grid(int64_t n, int batch) {
 // ct_idt_u8 only: which image the bytes stand for, where the float64 working image lives and what the last sweep writes
 struct IdtU8 {
     int input_f32;
-    double *out_f64;     // or NULL: the working image is `state` and the last sweep does not store it
-    IdtSinks sinks;
+    U8Sinks sinks;       // f64 NULL: the working image is `state` and the last sweep does not store it
     double *psnr_out;
 };
 
@@ -734,7 +708,7 @@ static size_t idt_u8_sq_bytes(int batch) { return (size_t)batch * kMaxBlocksPerI
 static size_t idt_u8_state_bytes(int batch, int64_t n_t) { return ((size_t)batch * (size_t)n_t * 3 * sizeof(double) + 15) & ~(size_t)15; }
 
 // T = float / double: u8 == NULL, `out` is the result and the working image.  T = uint8_t: `out` is the working image
-// (u8->out_f64 or the workspace) and the last iteration's apply sweep is the LAST form.
+// (u8->sinks.f64 or the workspace) and the last iteration's apply sweep is the LAST form.
 template <typename T>
 static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_r, int batch, const double *rot,
                     const double *rinv, int n_iter, int bins, int round_dr_f32, double *out, void *ws, size_t ws_bytes,
@@ -751,7 +725,7 @@ static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_
     if (n_iter == 0) return CT_E_BADARG;   // the host returns the input untouched in that case
     if (n_t == 0) return CT_OK;
     const int input_f32 = U8 ? u8->input_f32 : 0;
-    const IdtSinks no_sinks = {nullptr, nullptr, nullptr, nullptr};
+    const U8Sinks no_sinks = {nullptr, nullptr, nullptr, nullptr, nullptr};
     { const int zr = zero_async(ws, l.zero_bytes, s); if (zr) return zr; }
     // the tiled sweeps (uint8 in, or the last one of ct_idt_u8) take 1024 pixels per workgroup and pass
     const int gt = idt_apply_grid(n_t, batch), gt_tiled = idt_apply_grid(n_t / 4 + 1, batch);
@@ -793,11 +767,11 @@ static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_
         if constexpr (U8) {
             if (it == n_iter - 1) {         // the last sweep: the requested outputs and the metric partials
                 if (it == 0)
-                    hipLaunchKernelGGL((idt_apply_kernel<T, true>), dim3(gt_tiled, batch), dim3(kIdtBlock), lds, s, target, u8->out_f64, n_t,
+                    hipLaunchKernelGGL((idt_apply_kernel<T, true>), dim3(gt_tiled, batch), dim3(kIdtBlock), lds, s, target, u8->sinks.f64, n_t,
                                        rot, rinv, l.lut, n_iter, it, bins, rf, l.mm, input_f32, u8->sinks);
                 else
                     hipLaunchKernelGGL((idt_apply_kernel<double, true>), dim3(gt_tiled, batch), dim3(kIdtBlock), lds, s, (const double *)out,
-                                       u8->out_f64, n_t, rot, rinv, l.lut, n_iter, it, bins, rf, l.mm, input_f32, u8->sinks);
+                                       u8->sinks.f64, n_t, rot, rinv, l.lut, n_iter, it, bins, rf, l.mm, input_f32, u8->sinks);
                 CT_CHECK_LAUNCH();
                 continue;
             }
@@ -813,7 +787,7 @@ static int idt_impl(const T *target, int64_t n_t, const T *reference, int64_t n_
     }
     if constexpr (U8) {
         if (u8->sinks.gt) {
-            const int rc = launch_psnr_finish(u8->sinks.sq, gt_tiled, n_t * 3, batch, u8->psnr_out, s);
+            const int rc = launch_psnr_finish(u8->sinks.sq, gt_tiled, kMaxBlocksPerImage, n_t * 3, batch, u8->psnr_out, s);
             if (rc) return rc;
         }
     }
@@ -866,21 +840,15 @@ int ct_idt_u8(const uint8_t *target, int64_t n_t, const uint8_t *reference, int6
               const double *rot, const double *rinv, int n_iter, int bins, int input_f32, int round_dr_f32, double *out_f64,
               float *out_f32, uint8_t *out_u8, double *psnr_out, void *ws, size_t ws_bytes, const ct_idt_debug *dbg, void *stream) {
     if (n_t < 0 || n_r < 0 || batch < 0 || n_iter < 1 || bins < 1 || bins > ct::kIdtMaxBins) return CT_E_BADARG;
-    if (!out_f64 && !out_f32 && !out_u8) return CT_E_BADARG;
-    if (gt && batch > 0 && !psnr_out) return CT_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(out_f64) & 7) || (reinterpret_cast<uintptr_t>(out_f32) & 3) || (reinterpret_cast<uintptr_t>(psnr_out) & 7))
-        return CT_E_ALIGN;
+    const int rc = ct::check_u8_outputs(batch > 0 ? gt : nullptr, out_f64, out_f32, out_u8, psnr_out);   // an empty batch has no metric
+    if (rc) return rc;
     if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15)) return CT_E_WORKSPACE;
     const size_t base = ct_idt_workspace_bytes(batch, n_iter, bins);
     if (ws_bytes < ct_idt_u8_workspace_bytes(batch, n_iter, bins, n_t, out_f64 ? 0 : 1)) return CT_E_WORKSPACE;
     char *w = reinterpret_cast<char *>(ws);
     ct::IdtU8 u;
     u.input_f32 = input_f32 ? 1 : 0;
-    u.out_f64 = out_f64;
-    u.sinks.f32 = out_f32;
-    u.sinks.u8 = out_u8;
-    u.sinks.gt = gt;
-    u.sinks.sq = reinterpret_cast<double *>(w + base);
+    u.sinks = {out_f64, out_f32, out_u8, gt, reinterpret_cast<double *>(w + base)};
     u.psnr_out = psnr_out;
     double *state = out_f64 ? out_f64 : reinterpret_cast<double *>(w + base + ct::idt_u8_sq_bytes(batch));
     return ct::idt_impl<uint8_t>(target, n_t, reference, n_r, batch, rot, rinv, n_iter, bins, round_dr_f32, state, ws, ws_bytes, dbg,

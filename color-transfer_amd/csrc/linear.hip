@@ -479,7 +479,7 @@ static int reinhard_f32_impl(bool psnr, const float *target, const float *refere
     if (sq_blocks == 0) {                       // exact path: a sweep of its own over (out, gt)
         if ((rc = launch_sqerr_partials(out, gt, n_pixels * 3, batch, sq, &sq_blocks, s))) return rc;
     }
-    return launch_psnr_finish(sq, sq_blocks, n_pixels * 3, batch, psnr_out, s);
+    return launch_psnr_finish(sq, sq_blocks, kMaxBlocksPerImage, n_pixels * 3, batch, psnr_out, s);
 }
 
 // the persistent launch by name (any frame size it supports; the automatic dispatch above only takes frames that fill every wave)

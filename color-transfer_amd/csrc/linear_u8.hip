@@ -18,6 +18,7 @@
 #include "ct_metrics.h"
 #include "ct_moments.h"
 #include "ct_quant.h"
+#include "ct_u8_frames.h"
 
 namespace ct {
 
@@ -188,11 +189,7 @@ __global__ __launch_bounds__(kBlock) void affine_u8_kernel(const uint8_t *in, co
         o2 = (float)(fma(d2, A[8], fma(d1, A[5], d0 * A[2])) + mr[2]);
     };
     double acc[1] = {0.0};
-    auto sqerr = [&](float v, unsigned int kgt) {
-        const float c = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
-        const double d = (double)c - (double)tabf[kgt];
-        acc[0] += d * d;
-    };
+    auto sqerr = [&](float v, unsigned int kgt) { acc[0] += sq_err(v, [&] { return tabf[kgt]; }); };
 
     const int h = head_pixels(p, n_pixels);
     const int64_t n_chunks = (n_pixels - h) >> 4;
@@ -362,10 +359,9 @@ int ct_mk_u8(const uint8_t *target, const uint8_t *reference, const uint8_t *gt,
     int rc = ct::check_image_args(target, n_pixels, batch);
     if (rc) return rc;
     if ((rc = ct::check_image_args(reference, n_pixels, batch))) return rc;
-    if (out_f32 == nullptr && out_u8 == nullptr) return CT_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(out_f32) % sizeof(float)) return CT_E_ALIGN;
+    if ((rc = ct::check_u8_outputs(nullptr, nullptr, out_f32, out_u8, nullptr))) return rc;
     if (n_pixels > ct::kMaxPixelsU8 || decomposition < 0 || decomposition > 2) return CT_E_BADARG;
-    if (gt != nullptr && batch > 0 && psnr_out == nullptr) return CT_E_BADARG;
+    if ((rc = ct::check_u8_outputs(batch > 0 ? gt : nullptr, nullptr, out_f32, out_u8, psnr_out))) return rc;   // the metric's rule comes last
     if (ws == nullptr || (reinterpret_cast<uintptr_t>(ws) & 15) || ws_bytes < ct::ws_bytes_mk_u8(batch)) return CT_E_WORKSPACE;
     if (batch == 0 || n_pixels == 0) return CT_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -377,7 +373,7 @@ int ct_mk_u8(const uint8_t *target, const uint8_t *reference, const uint8_t *gt,
     int sq_blocks = 0;
     if ((rc = ct::launch_affine_u8(target, w.coef, out_f32, out_u8, gt, w.sq, &sq_blocks, n_pixels, batch, s))) return rc;
     if (gt == nullptr) return CT_OK;
-    return ct::launch_psnr_finish(w.sq, sq_blocks, n_pixels * 3, batch, psnr_out, s);
+    return ct::launch_psnr_finish(w.sq, sq_blocks, ct::kMaxBlocksPerImage, n_pixels * 3, batch, psnr_out, s);
 }
 
 }  // extern "C"

@@ -240,11 +240,11 @@ __global__ __launch_bounds__(kBlock) void sqerr_partial_kernel(const float *__re
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * kMaxBlocksPerImage + blockIdx.x] = s[0];
 }
 
-__global__ __launch_bounds__(kBlock) void psnr_finish_kernel(const double *__restrict__ partials, int n_blocks, int64_t n,
+__global__ __launch_bounds__(kBlock) void psnr_finish_kernel(const double *__restrict__ partials, int n_blocks, int stride, int64_t n,
                                                              double *__restrict__ out) {
     __shared__ double lds[4];
     double s[1] = {0.0};
-    for (int i = threadIdx.x; i < n_blocks; i += kBlock) s[0] += partials[(size_t)blockIdx.x * kMaxBlocksPerImage + i];
+    for (int i = threadIdx.x; i < n_blocks; i += kBlock) s[0] += partials[(size_t)blockIdx.x * stride + i];
     block_sum<1>(s, lds);
     if (threadIdx.x == 0) {
         const double mse = s[0] / (double)n;
@@ -261,8 +261,8 @@ int launch_sqerr_partials(const float *a, const float *b, int64_t n, int batch, 
     return CT_OK;
 }
 
-int launch_psnr_finish(const double *partials, int n_blocks, int64_t n, int batch, double *out, hipStream_t s) {
-    hipLaunchKernelGGL(psnr_finish_kernel, dim3(batch), dim3(kBlock), 0, s, partials, n_blocks, n, out);
+int launch_psnr_finish(const double *partials, int n_blocks, int stride, int64_t n, int batch, double *out, hipStream_t s) {
+    hipLaunchKernelGGL(psnr_finish_kernel, dim3(batch), dim3(kBlock), 0, s, partials, n_blocks, stride, n, out);
     CT_CHECK_LAUNCH();
     return CT_OK;
 }
@@ -319,7 +319,7 @@ int ct_frame_psnr_f32(const float *a, const float *b, int64_t n_elems, int batch
     int G = 0;
     const int rc = ct::launch_sqerr_partials(a, b, n_elems, batch, (double *)ws, &G, (hipStream_t)stream);
     if (rc) return rc;
-    return ct::launch_psnr_finish((const double *)ws, G, n_elems, batch, out, (hipStream_t)stream);
+    return ct::launch_psnr_finish((const double *)ws, G, ct::kMaxBlocksPerImage, n_elems, batch, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -19,56 +19,30 @@
 //
 // ct_regrain_u8 / ct_acg_u8 (uint8 target in; float64, float32 and / or bytes out, + PSNR): level 0's img_in is the target itself,
 // so the kernels that read it there (weights, the level-0 sweeps, the first down-resize) are instantiated for uint8_t: a byte is
-// looked up in the 256-entry float64 table of ct_idt_u8 (rg_fill_table) and then takes the float64 statements as they stand --
-// bitwise the float64 entry on the image the bytes stand for.  The LAST level-0 launch (<., true>) writes the requested outputs
-// and the squared-error partials of the metric (rg_emit) instead of the float64 iterate.
+// looked up in the 256-entry float64 table of the image it stands for (ct_bytes.h: fill_u8_table, ld_u8) and then takes the float64
+// statements as they stand -- bitwise the float64 entry on that image.  The LAST level-0 launch (<., true>) writes the requested
+// outputs and the squared-error partials of the metric (ct_u8_frames.h: U8Sinks, through rg_emit) instead of the float64 iterate.
+#include "ct_bytes.h"
 #include "ct_common.h"
+#include "ct_metrics.h"
 #include "ct_quant.h"
+#include "ct_u8_frames.h"
 
 namespace ct {
 
 constexpr int kRgMaxLevels = 8;
 
-// ---- uint8 img_in (level 0 of ct_regrain_u8 / ct_acg_u8) ------------------------------------------------------------------
-template <typename T> struct RgU8 { static constexpr bool v = false; };
-template <> struct RgU8<uint8_t> { static constexpr bool v = true; };
-
-// the table of idt.hip's idt_fill_table: byte k stands for (double)((float)k / 255.0f) (input_f32) or (double)k / 255.0.
-// By the 256 threads of the workgroup (kBlock == 256); the caller's next barrier publishes it.
-__device__ __forceinline__ void rg_fill_table(double *tab, int input_f32) {
-    tab[threadIdx.x & 255] = input_f32 ? (double)((float)(threadIdx.x & 255) / 255.0f) : (double)(threadIdx.x & 255) / 255.0;
-}
-template <typename T> __device__ __forceinline__ double rg_ld(const T *p, size_t e, const double *tab) {
-    if constexpr (RgU8<T>::v) return tab[p[e]];
-    else return p[e];
-}
-
-// What the LAST level-0 launch writes instead of the float64 iterate: any of the float64 result, that value rounded once to
-// float32, its bytes by ct_quant.h's rule, and per workgroup one float64 partial sum of (clamp(float32 result, 0, 1) - gt)^2,
-// gt as float32 k / 255 (IEEE division), added per thread in pixel order and then by block_sum's fixed tree.
-struct RgSinks {
-    double *f64;         // [batch][H][W][3] or NULL
-    float *f32;          // likewise
-    uint8_t *u8;         // likewise
-    const uint8_t *gt;   // likewise
-    double *sq;          // [batch][gridDim.x of the last launch], written when gt is given
-};
-
-// element e (over the whole batch) of the result
-__device__ __forceinline__ void rg_emit(const RgSinks &sk, size_t e, double y, double &acc) {
+// element e (over the whole batch) of the result, to the sinks of the LAST level-0 launch
+__device__ __forceinline__ void rg_emit(const U8Sinks &sk, size_t e, double y, double &acc) {
     if (sk.f64) sk.f64[e] = y;
     const float v = (float)y;
     if (sk.f32) sk.f32[e] = v;
     if (sk.u8) sk.u8[e] = (uint8_t)quant_u8(v);
-    if (sk.gt) {
-        const float c = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
-        const double d = (double)c - (double)((float)sk.gt[e] / 255.0f);
-        acc += d * d;
-    }
+    if (sk.gt) acc += sq_err(v, [&] { return (float)sk.gt[e] / 255.0f; });
 }
 
-// uniform over the grid (sk.gt is): one partial per workgroup
-__device__ __forceinline__ void rg_publish(const RgSinks &sk, double (&acc)[1], double *red) {
+// uniform over the grid (sk.gt is): one partial per workgroup, sk.sq [batch][gridDim.x of this launch]
+__device__ __forceinline__ void rg_publish(const U8Sinks &sk, double (&acc)[1], double *red) {
     if (sk.gt) {
         block_sum<1>(acc, red);
         if (threadIdx.x == 0) sk.sq[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = acc[0];
@@ -99,9 +73,9 @@ __device__ __forceinline__ int reflect_idx(int coord, int dim) {
 template <typename T>
 __global__ __launch_bounds__(kBlock) void rg_gauss_kernel(const T *__restrict__ in_, double *__restrict__ out_, int H, int W, int axis,
                                                          int radius, const double w0, const double w1, const double w2, int input_f32) {
-    __shared__ double tab[RgU8<T>::v ? 256 : 1];
-    if constexpr (RgU8<T>::v) {
-        rg_fill_table(tab, input_f32);
+    __shared__ double tab[IsU8<T>::v ? 256 : 1];
+    if constexpr (IsU8<T>::v) {
+        fill_u8_table(tab, input_f32, true);
         __syncthreads();
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -116,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void rg_gauss_kernel(const T *__restrict__ 
         const int rr = axis == 0 ? mirror_idx(r + k, H) : r, cc = axis == 1 ? mirror_idx(c + k, W) : c;
         const size_t p = ((size_t)rr * W + cc) * 3;
         const double g = wk[k < 0 ? -k : k];
-        acc[0] += g * rg_ld(in, p, tab); acc[1] += g * rg_ld(in, p + 1, tab); acc[2] += g * rg_ld(in, p + 2, tab);
+        acc[0] += g * ld_u8(in, p, tab); acc[1] += g * ld_u8(in, p + 1, tab); acc[2] += g * ld_u8(in, p + 2, tab);
     }
     double *o = out + (size_t)i * 3;
     o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
@@ -126,9 +100,9 @@ __global__ __launch_bounds__(kBlock) void rg_gauss_kernel(const T *__restrict__ 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void rg_bilinear_kernel(const T *__restrict__ in_, double *__restrict__ out_, int Hi, int Wi, int Ho,
                                                             int Wo, double fr, double fc, int input_f32) {
-    __shared__ double tab[RgU8<T>::v ? 256 : 1];
-    if constexpr (RgU8<T>::v) {
-        rg_fill_table(tab, input_f32);
+    __shared__ double tab[IsU8<T>::v ? 256 : 1];
+    if constexpr (IsU8<T>::v) {
+        fill_u8_table(tab, input_f32, true);
         __syncthreads();
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -145,8 +119,8 @@ __global__ __launch_bounds__(kBlock) void rg_bilinear_kernel(const T *__restrict
     double *o = out + (size_t)i * 3;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const double top = (1.0 - dc) * rg_ld(in, p00 + ch, tab) + dc * rg_ld(in, p01 + ch, tab);
-        const double bottom = (1.0 - dc) * rg_ld(in, p10 + ch, tab) + dc * rg_ld(in, p11 + ch, tab);
+        const double top = (1.0 - dc) * ld_u8(in, p00 + ch, tab) + dc * ld_u8(in, p01 + ch, tab);
+        const double bottom = (1.0 - dc) * ld_u8(in, p10 + ch, tab) + dc * ld_u8(in, p11 + ch, tab);
         o[ch] = (1.0 - dr) * top + dr * bottom;
     }
 }
@@ -156,9 +130,9 @@ __global__ __launch_bounds__(kBlock) void rg_bilinear_kernel(const T *__restrict
 template <typename T>
 __global__ __launch_bounds__(kBlock) void rg_weights_kernel(const T *__restrict__ in_, double2 *__restrict__ wt_, int H, int W, double phi_scale,
                                                            int input_f32) {
-    __shared__ double tab[RgU8<T>::v ? 256 : 1];
-    if constexpr (RgU8<T>::v) {
-        rg_fill_table(tab, input_f32);
+    __shared__ double tab[IsU8<T>::v ? 256 : 1];
+    if constexpr (IsU8<T>::v) {
+        fill_u8_table(tab, input_f32, true);
         __syncthreads();
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -171,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void rg_weights_kernel(const T *__restrict_
     double s = 0.0;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const double dx = rg_ld(in, pr + ch, tab) - rg_ld(in, pl + ch, tab), dy = rg_ld(in, pd + ch, tab) - rg_ld(in, pu + ch, tab);
+        const double dx = ld_u8(in, pr + ch, tab) - ld_u8(in, pl + ch, tab), dy = ld_u8(in, pd + ch, tab) - ld_u8(in, pu + ch, tab);
         s += dx * dx + dy * dy;
     }
     const double delta = sqrt(s);
@@ -185,11 +159,11 @@ __global__ __launch_bounds__(kBlock) void rg_weights_kernel(const T *__restrict_
 template <typename T, bool LAST>
 __global__ __launch_bounds__(kBlock) void rg_sweep_kernel(const double *__restrict__ prev_, const T *__restrict__ in_, const double *__restrict__ col_,
                                                          const double2 *__restrict__ wt_, double *__restrict__ next_, int H, int W, int input_f32,
-                                                         RgSinks sk) {
-    __shared__ double tab[RgU8<T>::v ? 256 : 1];
+                                                         U8Sinks sk) {
+    __shared__ double tab[IsU8<T>::v ? 256 : 1];
     __shared__ double red[LAST ? 4 : 1];
-    if constexpr (RgU8<T>::v) {
-        rg_fill_table(tab, input_f32);
+    if constexpr (IsU8<T>::v) {
+        fill_u8_table(tab, input_f32, true);
         __syncthreads();
     }
     const size_t f0 = (size_t)blockIdx.y * H * W;                   // this frame, in pixels
@@ -214,10 +188,10 @@ __global__ __launch_bounds__(kBlock) void rg_sweep_kernel(const double *__restri
         const double scale = (1 - rho) / (den + eps);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            const double x = rg_ld(in, i * 3 + ch, tab);
-            const double num = psi * col[i * 3 + ch] + phi1 * (prev[iR * 3 + ch] - rg_ld(in, iR * 3 + ch, tab) + x) +
-                               phi2 * (prev[iD * 3 + ch] - rg_ld(in, iD * 3 + ch, tab) + x) + phi3 * (prev[iL * 3 + ch] - rg_ld(in, iL * 3 + ch, tab) + x) +
-                               phi4 * (prev[iU * 3 + ch] - rg_ld(in, iU * 3 + ch, tab) + x);
+            const double x = ld_u8(in, i * 3 + ch, tab);
+            const double num = psi * col[i * 3 + ch] + phi1 * (prev[iR * 3 + ch] - ld_u8(in, iR * 3 + ch, tab) + x) +
+                               phi2 * (prev[iD * 3 + ch] - ld_u8(in, iD * 3 + ch, tab) + x) + phi3 * (prev[iL * 3 + ch] - ld_u8(in, iL * 3 + ch, tab) + x) +
+                               phi4 * (prev[iU * 3 + ch] - ld_u8(in, iU * 3 + ch, tab) + x);
             const double y = num * scale + rho * prev[i * 3 + ch];
             if constexpr (LAST) rg_emit(sk, (f0 + i) * 3 + ch, y, acc[0]);
             else next[i * 3 + ch] = y;
@@ -243,12 +217,12 @@ constexpr int kRgPxPerThread = kRgMaxRegion / kBlock;   // 6
 template <typename T, bool LAST>
 __global__ __launch_bounds__(kBlock) void rg_sweepk_kernel(const double *__restrict__ prev_, const T *__restrict__ in_, const double *__restrict__ col_,
                                                           const double2 *__restrict__ wt_, double *__restrict__ next_, int H, int W, int th, int tw,
-                                                          int k, int tiles_x, int input_f32, RgSinks sk) {
+                                                          int k, int tiles_x, int input_f32, U8Sinks sk) {
     extern __shared__ double lds[];
-    __shared__ double tab[RgU8<T>::v ? 256 : 1];
+    __shared__ double tab[IsU8<T>::v ? 256 : 1];
     __shared__ double red[LAST ? 4 : 1];
-    if constexpr (RgU8<T>::v) {
-        rg_fill_table(tab, input_f32);
+    if constexpr (IsU8<T>::v) {
+        fill_u8_table(tab, input_f32, true);
         __syncthreads();
     }
     const size_t f0 = (size_t)blockIdx.y * H * W;                   // this frame, in pixels
@@ -275,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void rg_sweepk_kernel(const double *__restr
             phiL[p] = w0.y;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
-                inr[j][ch] = rg_ld(in, g * 3 + ch, tab); cur[j][ch] = prev[g * 3 + ch]; pc[j][ch] = col[g * 3 + ch];
+                inr[j][ch] = ld_u8(in, g * 3 + ch, tab); cur[j][ch] = prev[g * 3 + ch]; pc[j][ch] = col[g * 3 + ch];
                 dA[p * 3 + ch] = cur[j][ch] - inr[j][ch];
             }
             // image clamping == region clamping wherever the region edge is an image edge; elsewhere: halo garbage
@@ -341,11 +315,11 @@ __global__ __launch_bounds__(kBlock) void rg_sweepk_kernel(const double *__restr
 
 // the image itself as the result (nbits[0] == 0), or the bytes as the float64 start image of a one-level pyramid
 template <typename T>
-__global__ __launch_bounds__(kBlock) void rg_emit_kernel(const T *__restrict__ src, int64_t n_px, int input_f32, RgSinks sk) {
-    __shared__ double tab[RgU8<T>::v ? 256 : 1];
+__global__ __launch_bounds__(kBlock) void rg_emit_kernel(const T *__restrict__ src, int64_t n_px, int input_f32, U8Sinks sk) {
+    __shared__ double tab[IsU8<T>::v ? 256 : 1];
     __shared__ double red[4];
-    if constexpr (RgU8<T>::v) {
-        rg_fill_table(tab, input_f32);
+    if constexpr (IsU8<T>::v) {
+        fill_u8_table(tab, input_f32, true);
         __syncthreads();
     }
     const size_t f0 = (size_t)blockIdx.y * n_px;
@@ -353,23 +327,9 @@ __global__ __launch_bounds__(kBlock) void rg_emit_kernel(const T *__restrict__ s
     double acc[1] = {0.0};
     if (i < n_px) {
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) rg_emit(sk, (f0 + i) * 3 + ch, rg_ld(src, (f0 + i) * 3 + ch, tab), acc[0]);
+        for (int ch = 0; ch < 3; ++ch) rg_emit(sk, (f0 + i) * 3 + ch, ld_u8(src, (f0 + i) * 3 + ch, tab), acc[0]);
     }
     rg_publish(sk, acc, red);
-}
-
-// out[frame] = {mse, PSNR} from n_parts partial sums per frame, added in a fixed order (metrics.hip's psnr_finish_kernel on
-// partials[frame][n_parts]: the tiled sweep of a large frame has more workgroups than kMaxBlocksPerImage).  grid = batch
-__global__ __launch_bounds__(kBlock) void rg_psnr_finish_kernel(const double *__restrict__ partials, int n_parts, int64_t n, double *__restrict__ out) {
-    __shared__ double red[4];
-    double s[1] = {0.0};
-    for (int i = threadIdx.x; i < n_parts; i += kBlock) s[0] += partials[(size_t)blockIdx.x * n_parts + i];
-    block_sum<1>(s, red);
-    if (threadIdx.x == 0) {
-        const double mse = s[0] / (double)n;
-        out[blockIdx.x * 2] = mse;
-        out[blockIdx.x * 2 + 1] = 10.0 * log10(1.0 / (mse > 1e-300 ? mse : 1e-300));
-    }
 }
 
 struct RgLevel { int h, w; };
@@ -459,9 +419,9 @@ template <typename T, bool LAST> static hipError_t rg_sweepk_attr() {
 // the last level).
 template <typename T>
 static int rg_relax(const double *start, const T *in, const double *col, double2 *wt, double *it_a, double *it_b, int h, int w, int level, int n_sweeps,
-                    bool last, int batch, int input_f32, const RgSinks &sk, const double **result, int *n_parts, hipStream_t s) {
+                    bool last, int batch, int input_f32, const U8Sinks &sk, const double **result, int *n_parts, hipStream_t s) {
     const int64_t px = (int64_t)h * w;
-    const RgSinks none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const U8Sinks none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipLaunchKernelGGL((rg_weights_kernel<T>), rg_grid(px, batch), dim3(kBlock), 0, s, in, wt, h, w, 30.0 * exp2(-(double)level), input_f32);
     CT_CHECK_LAUNCH();
     const double *prev = start;
@@ -510,8 +470,8 @@ static int rg_relax(const double *start, const T *in, const double *col, double2
 // published workspace layout).  T = uint8_t: img_in are the bytes of the target.  sk.sq is set here.
 template <typename T>
 static int rg_run(const T *img_in, const double *img_col, int batch, int height, int width, int input_f32, const int *nbits, int n_nbits,
-                  bool l0_copies, RgSinks sk, double *psnr_out, void *ws, hipStream_t s) {
-    constexpr bool U8 = RgU8<T>::v;
+                  bool l0_copies, U8Sinks sk, double *psnr_out, void *ws, hipStream_t s) {
+    constexpr bool U8 = IsU8<T>::v;
     if (rg_sweepk_attr<double, false>() != hipSuccess || rg_sweepk_attr<T, false>() != hipSuccess || rg_sweepk_attr<T, true>() != hipSuccess)
         return CT_E_BADARG;
     RgLevel lv[kRgMaxLevels];
@@ -544,7 +504,7 @@ static int rg_run(const T *img_in, const double *img_col, int batch, int height,
         }
     }
     sk.sq = p;
-    const RgSinks none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const U8Sinks none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const double *coarse = nullptr;                                    // the solution of level l + 1
     int n_parts = 0;
     for (int l = n - 1; l >= 0; --l) {
@@ -557,7 +517,7 @@ static int rg_run(const T *img_in, const double *img_col, int batch, int height,
         } else if (l > 0) {
             start = in_l[l];                                           // iterative.py:74: img_arr_out = img_arr_in
         } else if constexpr (U8) {                                     // a one-level pyramid: the bytes as the float64 start image
-            RgSinks as_f64 = none;
+            U8Sinks as_f64 = none;
             as_f64.f64 = it_a[0];
             hipLaunchKernelGGL((rg_emit_kernel<uint8_t>), rg_grid((int64_t)h * w, batch), dim3(kBlock), 0, s, img_in, (int64_t)h * w, input_f32, as_f64);
             CT_CHECK_LAUNCH();
@@ -571,19 +531,8 @@ static int rg_run(const T *img_in, const double *img_col, int batch, int height,
                                                  &n_parts, s);
         if (rc) return rc;
     }
-    if (sk.gt) {
-        hipLaunchKernelGGL(rg_psnr_finish_kernel, dim3(batch), dim3(kBlock), 0, s, sk.sq, n_parts, (int64_t)height * width * 3, psnr_out);
-        CT_CHECK_LAUNCH();
-    }
-    return CT_OK;
-}
-
-// the argument rules the byte entries share (those of ct_idt_u8); 0 or the error
-static int rg_check_outputs(const void *gt, const double *out_f64, const float *out_f32, const uint8_t *out_u8, const double *psnr_out) {
-    if (!out_f64 && !out_f32 && !out_u8) return CT_E_BADARG;
-    if (gt && !psnr_out) return CT_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(out_f64) & 7) || (reinterpret_cast<uintptr_t>(out_f32) & 3) || (reinterpret_cast<uintptr_t>(psnr_out) & 7))
-        return CT_E_ALIGN;
+    // the tiled sweep of a large frame has more workgroups than kMaxBlocksPerImage: the rows of sk.sq are n_parts apart
+    if (sk.gt) return launch_psnr_finish(sk.sq, n_parts, n_parts, (int64_t)height * width * 3, batch, psnr_out, s);
     return CT_OK;
 }
 
@@ -616,7 +565,7 @@ int ct_regrain_f64(const double *img_in, const double *img_col, double *out, int
     if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15) || ws_bytes < ct_regrain_workspace_bytes(height, width)) return CT_E_WORKSPACE;
     if (!rg_size_ok(1, height, width, n_nbits) || !rg_nbits_ok(nbits, n_nbits)) return CT_E_BADARG;
     if (ws_bytes < (rg_ws_doubles(1, height, width, n_nbits, true) - rg_parts(height, width)) * sizeof(double)) return CT_E_WORKSPACE;   // more than 6 levels
-    const RgSinks sk = {out, nullptr, nullptr, nullptr, nullptr};
+    const U8Sinks sk = {out, nullptr, nullptr, nullptr, nullptr};
     return rg_run<double>(img_in, img_col, 1, height, width, 0, nbits, n_nbits, true, sk, nullptr, ws, (hipStream_t)stream);
 }
 
@@ -630,10 +579,10 @@ int ct_regrain_u8(const uint8_t *img_in, const double *img_col, int batch, int h
     using namespace ct;
     if (!img_in || !img_col || !rg_size_ok(batch, height, width, n_nbits) || !rg_nbits_ok(nbits, n_nbits)) return CT_E_BADARG;
     if (reinterpret_cast<uintptr_t>(img_col) & 7) return CT_E_ALIGN;
-    const int rc = rg_check_outputs(gt, out_f64, out_f32, out_u8, psnr_out);
+    const int rc = check_u8_outputs(gt, out_f64, out_f32, out_u8, psnr_out);
     if (rc) return rc;
     if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15) || ws_bytes < ct_regrain_u8_workspace_bytes(batch, height, width, n_nbits)) return CT_E_WORKSPACE;
-    const RgSinks sk = {out_f64, out_f32, out_u8, gt, nullptr};
+    const U8Sinks sk = {out_f64, out_f32, out_u8, gt, nullptr};
     return rg_run<uint8_t>(img_in, img_col, batch, height, width, input_f32 ? 1 : 0, nbits, n_nbits, false, sk, psnr_out, ws, (hipStream_t)stream);
 }
 
@@ -660,7 +609,7 @@ int ct_acg_u8(const uint8_t *target, const uint8_t *reference, int64_t n_r, cons
         return CT_E_BADARG;
     const size_t need = ct_acg_u8_workspace_bytes(batch, height, width, n_iter, bins, n_nbits);
     if (need == 0) return CT_E_BADARG;                                 // bins
-    const int rc = rg_check_outputs(gt, out_f64, out_f32, out_u8, psnr_out);
+    const int rc = check_u8_outputs(gt, out_f64, out_f32, out_u8, psnr_out);
     if (rc) return rc;
     if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15) || ws_bytes < need) return CT_E_WORKSPACE;
     char *w = reinterpret_cast<char *>(ws);
@@ -670,7 +619,7 @@ int ct_acg_u8(const uint8_t *target, const uint8_t *reference, int64_t n_r, cons
     const int ri = ct_idt_u8(target, (int64_t)height * width, reference, n_r, nullptr, batch, rot, rinv, n_iter, bins, f32, f32, graded, nullptr, nullptr,
                              nullptr, ws, idt_bytes, nullptr, stream);
     if (ri) return ri;
-    const RgSinks sk = {out_f64, out_f32, out_u8, gt, nullptr};
+    const U8Sinks sk = {out_f64, out_f32, out_u8, gt, nullptr};
     return rg_run<uint8_t>(target, graded, batch, height, width, f32, nbits, n_nbits, false, sk, psnr_out, w + idt_bytes + acg_state_bytes(batch, height, width),
                            (hipStream_t)stream);
 }

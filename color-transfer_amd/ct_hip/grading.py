@@ -7,7 +7,8 @@ import torch
 
 from ._core import (CT_WS_IDT, CtHipError, SIGNATURES, _c_i64, _c_int, _c_p, _c_sz, _ptr, _stream, check, lib,
                     workspace)
-from .idt import _u8_frames, _u8_metric, _u8_outputs, _u8_rotations, _upload_rotations
+from ._u8 import _NULL, _out_ptrs, _result, _u8_bins, _u8_frames, _u8_metric, _u8_outputs, _u8_pair, _u8_rotations
+from .idt import _upload_rotations
 
 SIGNATURES.update({
     "ct_regrain_u8_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
@@ -18,7 +19,6 @@ SIGNATURES.update({
 })
 
 NBITS = (4, 16, 32, 64, 64, 64)                  # the reference's default (methods/iterative.py:62)
-_NULL = ctypes.c_void_p(0)
 
 
 def _nbits(nbits, fn):
@@ -37,16 +37,6 @@ def _splits(B, frames_per_call, fn):
     if isinstance(frames_per_call, bool) or not isinstance(frames_per_call, (int, np.integer)) or frames_per_call < 1:
         raise CtHipError("%s: frames_per_call must be a positive integer or None, got %r" % (fn, frames_per_call))
     return [(a, min(a + int(frames_per_call), B)) for a in range(0, B, int(frames_per_call))]
-
-
-def _result(target, out, outs, g, psnr_out):
-    res = tuple(o.view(tuple(target.shape)) for o in outs)
-    ret = res if isinstance(out, (tuple, list)) else res[0]
-    return (ret, psnr_out) if g is not None else ret
-
-
-def _out_ptrs(slots, shape, a, b):
-    return [(_ptr(slots[d].view(shape)[a:b]) if d in slots else _NULL) for d in (torch.float64, torch.float32, torch.uint8)]
 
 
 def regrain_u8(img_in_u8, img_col, nbits=NBITS, input_f32=True, out_dtype=torch.float64, out=None, gt=None, psnr_out=None,
@@ -91,14 +81,9 @@ def acg_u8(target, reference, rotations, bins=255, nbits=NBITS, input_f32=True, 
     as for ct_hip.idt_u8.  frames_per_call: the group goes through in sub-batches of that many frames, which bounds the workspace
     (at 1080p the float64 pyramid takes ~360 MB per frame); the result does not depend on it."""
     fn = "acg_u8"
-    x, r = _u8_frames(target, "target", fn), _u8_frames(reference, "reference", fn)
-    if x.device != r.device:
-        raise CtHipError("%s: target on %s, reference on %s" % (fn, x.device, r.device))
-    if x.shape[0] != r.shape[0]:
-        raise CtHipError("%s needs target/reference of one batch size, got %d and %d" % (fn, x.shape[0], r.shape[0]))
+    x, r = _u8_pair(target, reference, fn)
     B, h, w, n_r = x.shape[0], x.shape[1], x.shape[2], r.shape[1] * r.shape[2]
-    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= 1024:
-        raise CtHipError("%s: bins must be an integer in 1..1024, got %r" % (fn, bins))
+    bins = _u8_bins(bins, fn)
     rot = _u8_rotations(rotations, B, fn)
     nb = _nbits(nbits, fn)
     outs, slots = _u8_outputs(x, out, out_dtype, fn)
@@ -107,12 +92,12 @@ def acg_u8(target, reference, rotations, bins=255, nbits=NBITS, input_f32=True, 
     both, n_iter = _upload_rotations(rot, B, x.device)
     arr = (ctypes.c_int * len(nb))(*nb)
     for a, b in splits:
-        need = lib().ct_acg_u8_workspace_bytes(b - a, h, w, n_iter, int(bins), len(nb))
+        need = lib().ct_acg_u8_workspace_bytes(b - a, h, w, n_iter, bins, len(nb))
         if need == 0:
             raise CtHipError("%s: unsupported bins=%d / n_iter=%d / frame size %s" % (fn, bins, n_iter, tuple(x.shape)))
         ws = workspace(CT_WS_IDT, 0, b - a, x.device, need=need)
         p = _out_ptrs(slots, x.shape, a, b)
         check(lib().ct_acg_u8(_ptr(x[a:b]), _ptr(r[a:b]), n_r, _ptr(g[a:b]) if g is not None else _NULL, b - a, h, w, _ptr(both[0][a:b]),
-                              _ptr(both[1][a:b]), n_iter, int(bins), int(bool(input_f32)), ctypes.cast(arr, ctypes.c_void_p), len(nb),
+                              _ptr(both[1][a:b]), n_iter, bins, int(bool(input_f32)), ctypes.cast(arr, ctypes.c_void_p), len(nb),
                               p[0], p[1], p[2], _ptr(psnr_out.view(-1)[2 * a:]) if g is not None else _NULL, _ptr(ws), ws.numel(), _stream()))
     return _result(target, out, outs, g, psnr_out)

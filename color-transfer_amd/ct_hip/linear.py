@@ -7,6 +7,7 @@ import torch
 from ._core import (CT_LAB_STATS_STRIDE, CT_RGB_STATS_STRIDE, CT_WS_LAB_STATS, CT_WS_MK_U8, CT_WS_REINHARD, CT_WS_REINHARD_PERSIST,
                     CT_WS_REINHARD_PSNR, CT_WS_RGB_MEANCOV, CtHipError, SIGNATURES, _as_batch, _c_i64, _c_int, _c_p,
                     _c_sz, _ptr, _require_cuda, _stream, _suffix, _upload_small, check, lib, workspace)
+from ._u8 import _u8_metric
 
 SIGNATURES.update({
     "ct_profile_events": (None, [_c_p, _c_p, _c_p, _c_p]),
@@ -271,19 +272,7 @@ def _mk_u8(target, x, r, B, n, mode, out_dtype, out, gt, psnr_out):
     if out.dtype not in (torch.float32, torch.uint8):
         raise CtHipError("mk on uint8 frames writes float32 or uint8, not %s" % out.dtype)
     null = ctypes.c_void_p(0)
-    g = None
-    if gt is not None:
-        g, _ = _as_batch(gt)
-        _require_cuda(g)
-        if g.dtype != torch.uint8 or g.shape != x.shape:
-            raise CtHipError("gt must be uint8 frames of the images' shape, got %s %s" % (g.dtype, tuple(g.shape)))
-        if psnr_out is None:
-            psnr_out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
-        _require_cuda(psnr_out)
-        if psnr_out.dtype != torch.float64 or psnr_out.numel() < 2 * B:
-            raise CtHipError("psnr_out must be float64 with >= 2*B elements")
-    elif psnr_out is not None:
-        raise CtHipError("psnr_out without gt")
+    g, psnr_out = _u8_metric(x, gt, psnr_out, "mk")
     ws = workspace(CT_WS_MK_U8, n, B, x.device)
     f32, u8 = (_ptr(out), null) if out.dtype == torch.float32 else (null, _ptr(out))
     check(lib().ct_mk_u8(_ptr(x), _ptr(r), _ptr(g) if g is not None else null, f32, u8, _ptr(psnr_out) if g is not None else null,

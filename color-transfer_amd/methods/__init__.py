@@ -130,6 +130,17 @@ class Runner(torch.nn.Module):
             return self.grading_groups
         return self.func_spec == REINHARD_SPEC or (self.byte_groups and self.func_spec in (MK_SPEC, XIAO_SPEC))
 
+    def _group_buffer(self, group_u8, k):
+        """float32 [k][H][W][3] on the group's device: one buffer, kept and reused while the frame size fits"""
+        if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:
+            self._out = torch.empty((k,) + tuple(group_u8.shape[2:]), dtype=torch.float32, device=group_u8.device)
+        return self._out[:k]
+
+    def _iterative_u8(self):
+        """the grouped entry of an iterative method (the two have one signature), else None"""
+        import ct_hip
+        return {IDT_SPEC: ct_hip.idt_u8, ACG_SPEC: ct_hip.acg_u8}.get(self.func_spec)
+
     def test_group(self, group_u8, psnr_out):
         """group_u8: device uint8 [3 roles: target, reference, gt][k][H][W][3]; psnr_out: float64 [k, 2] rows of the caller's table,
         filled with (mse, PSNR) per frame -- Runner.test_step's clamp + piq.psnr (methods/__init__.py:30-32) for k frames in one
@@ -137,17 +148,12 @@ class Runner(torch.nn.Module):
         (moments of the bytes, the host SVDs, the affine map on the bytes) and ct_hip.frame_psnr."""
         import ct_hip
         k = group_u8.shape[1]
-        if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:
-            self._out = torch.empty((k,) + tuple(group_u8.shape[2:]), dtype=torch.float32, device=group_u8.device)
-        out = self._out[:k]
-        if self.func_spec == IDT_SPEC:
+        out = self._group_buffer(group_u8, k)
+        iterative_u8 = self._iterative_u8()
+        if iterative_u8 is not None:
             # one draw per frame in frame order, like forward()'s loop: a seeded np.random gives the per-frame route's matrices
             from methods.iterative import draw_group_rotations
-            ct_hip.idt_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out=out, gt=group_u8[2], psnr_out=psnr_out)
-            return out
-        if self.func_spec == ACG_SPEC:
-            from methods.iterative import draw_group_rotations
-            ct_hip.acg_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out=out, gt=group_u8[2], psnr_out=psnr_out)
+            iterative_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out=out, gt=group_u8[2], psnr_out=psnr_out)
             return out
         if self.func_spec == MK_SPEC:
             ct_hip.mk(group_u8[0], group_u8[1], out=out, gt=group_u8[2], psnr_out=psnr_out)
@@ -165,17 +171,13 @@ class Runner(torch.nn.Module):
         corrected frames as bytes already, uint8 [k][H][W][3], freshly allocated (the writer holds them until their download)."""
         import ct_hip
         k = group_u8.shape[1]
-        if self.func_spec == IDT_SPEC:
+        iterative_u8 = self._iterative_u8()
+        if iterative_u8 is not None:
             from methods.iterative import draw_group_rotations
-            return ct_hip.idt_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out_dtype=torch.uint8)
-        if self.func_spec == ACG_SPEC:
-            from methods.iterative import draw_group_rotations
-            return ct_hip.acg_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out_dtype=torch.uint8)
+            return iterative_u8(group_u8[0], group_u8[1], draw_group_rotations(k), input_f32=True, out_dtype=torch.uint8)
         if self.func_spec != REINHARD_SPEC:
             return self.func_cuda(group_u8[0], group_u8[1], out_dtype=torch.uint8)
-        if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:
-            self._out = torch.empty((k,) + tuple(group_u8.shape[2:]), dtype=torch.float32, device=group_u8.device)
-        return ct_hip.reinhard_persist(group_u8[0], group_u8[1], out=self._out[:k])
+        return ct_hip.reinhard_persist(group_u8[0], group_u8[1], out=self._group_buffer(group_u8, k))
 
     def forward(self, batch):
         target, reference = batch["target"], batch["reference"]

@@ -18,8 +18,8 @@ import sys
 import numpy as np
 import pytest
 
-from oracle import iterative as oit
 from oracle import regrain as org
+from tests.u8_common import ULP, dev, grouped_frames, image, per_frame_route, psnr_close, rotations, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -27,12 +27,7 @@ torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = os.path.join(ROOT, "color-transfer_amd", "configs")
 ACG_SPEC = "methods.iterative.automated_color_grading"
-ULP = 2.0 ** -53
 KINDS = (torch.float64, torch.float32, torch.uint8)
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, copy=True)).cuda()
 
 
 def scene(h, w, batch, seed):
@@ -50,25 +45,6 @@ def graded(k, seed):
     """a float64 image like an IDT result of the frames k: unclipped, near the frames"""
     rng = np.random.default_rng(seed)
     return (k / 255.0) ** 0.9 * 0.95 + 0.03 * rng.standard_normal(k.shape)
-
-
-def rotations(n_iter, seed, batch=None):
-    np.random.seed(seed)
-    return oit.draw_rotations(n_iter) if batch is None else np.stack([oit.draw_rotations(n_iter) for _ in range(batch)])
-
-
-def image(k, f32):
-    """the float image the bytes stand for"""
-    return k.astype(np.float32) / np.float32(255) if f32 else k / 255.0
-
-
-def bits(t):
-    """an integer view: equal bits, a NaN for the same NaN"""
-    return t.view({torch.float64: torch.int64, torch.float32: torch.int32}.get(t.dtype, t.dtype))
-
-
-def same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and bool(torch.equal(bits(a), bits(b)))
 
 
 def composition(t, r, rot, f32, nbits=None):
@@ -168,6 +144,30 @@ def test_outputs_and_metric(shape):
         print("%dx%d frame %d: mse %.17g, relative error %.3g (bound %.3g)" % (h, w, b, mse, err, 3 * n * ULP))
         assert err <= 3 * n * ULP
         assert abs(ps[b, 1] - 10 * np.log10(1 / mse)) <= 1e-12 * max(1.0, abs(ps[b, 1]))
+
+
+# The last launch writes one partial per workgroup and frame, frame b's from b * (workgroups per frame) on: more of them than the
+# 1024 that every other entry reserves per frame.  (360, 500), two sweeps: 45 x 32 = 1440 tiles of 8 x 16; (520, 520), one sweep: the
+# flat kernel's ceil(270400 / 256) = 1057.  One pyramid level each; the second frame's row stands behind the first frame's partials.
+@pytest.mark.parametrize("shape,nbits,parts", (((360, 500), (2,), 1440), ((520, 520), (1,), 1057)))
+def test_metric_past_1024_partials_per_frame(shape, nbits, parts):
+    import ct_hip
+    h, w = shape
+    n = h * w
+    tiled = nbits[0] > 1
+    assert not tiled or n <= 200000                                    # the 8 x 16 tiles of the smaller levels
+    assert 1024 < parts == (-(-h // 8) * -(-w // 16) if tiled else -(-n // 256))
+    tk, gk = scene(h, w, 2, 19), scene(h, w, 2, 20)
+    o32, psnr = ct_hip.regrain_u8(dev(tk), dev(graded(tk, 9)), nbits=nbits, out_dtype=torch.float32, gt=dev(gk))
+    assert o32.dtype == torch.float32 and psnr.dtype == torch.float64 and tuple(psnr.shape) == (2, 2)
+    o, ps = o32.cpu().numpy(), psnr.cpu().numpy()
+    for b in range(2):
+        d = np.clip(o[b], 0, 1).astype(np.float64) - (gk[b].astype(np.float32) / np.float32(255)).astype(np.float64)
+        mse = float(np.mean(d * d))
+        err = abs(ps[b, 0] - mse) / mse
+        print("%dx%d frame %d: mse %.17g, relative error %.3g (bound %.3g)" % (h, w, b, mse, err, 3 * n * ULP))
+        assert err <= 3 * n * ULP
+        assert psnr_close(ps[b, 1], 10 * np.log10(1 / mse), n)
 
 
 # ---------------------------------------------------------------------------------------------------- 4. batch independence
@@ -292,42 +292,11 @@ def test_refusals_launch_nothing():
 H, W, FRAMES, GROUP = 24, 40, 5, 3               # the IDT twin's loader: two groups, the second one ragged
 
 
-def grouped_frames(video):
-    """the frames as the grouped route sees them (a group's content is defined by its first frame): [(target, reference, gt)] uint8 HWC"""
-    out = []
-    for first in range(0, FRAMES, video.group):
-        chunk = video.host_chunk(first)
-        out += [tuple(chunk[i, j] for i in range(3)) for j in range(min(video.group, FRAMES - first))]
-    return out
-
-
-def per_frame_route(triples, seed):
-    """the per-frame Runner (forward, clamp, pack_u8; test_step) on a seeded np.random, for uint8 HWC (target, reference, gt) triples
-    made float32 CHW as the datasets make them: (bytes [n,H,W,3], rows [n,2] of (mse, PSNR) as methods.psnr computes them)"""
-    import ct_hip
-    from methods import Runner
-    model = Runner(ACG_SPEC, metrics="psnr")
-    assert not model.takes_groups()
-    batches = [{k: (x.permute(2, 0, 1).float() / 255)[None].cuda() for k, x in zip(("target", "reference", "gt"), tr)} for tr in triples]
-    np.random.seed(seed)
-    frames_u8 = [ct_hip.pack_u8(model(b).clamp(0, 1).contiguous(), "chw")[0].cpu().numpy() for b in batches]
-    np.random.seed(seed)
-    rows = [ct_hip.frame_psnr(model(b).clamp(0, 1).float().contiguous(), b["gt"].float().contiguous())[0].cpu().numpy() for b in batches]
-    return np.stack(frames_u8), np.stack(rows)
-
-
-def psnr_close(got, want, n):
-    """PSNR values of mse values that agree within 3 n 2^-53 relative: d(10 log10(1 / mse)) = 10 / ln 10 * d(mse) / mse, plus the
-    1e-12 relative that test_mk_psnr allows for the logarithm itself"""
-    got, want = np.asarray(got), np.asarray(want)
-    return bool((np.abs(got - want) <= 10 / np.log(10) * 3 * n * ULP + 1e-12 * np.maximum(1.0, np.abs(want))).all())
-
-
 def test_runner_groups():
     from methods import Runner
     from utils.data import SyntheticStereoVideoU8, prefetch_groups
     video = SyntheticStereoVideoU8(FRAMES, H, W, group=FRAMES, pool=2)
-    want8, want_psnr = per_frame_route(grouped_frames(video), 77)
+    want8, want_psnr = per_frame_route(ACG_SPEC, grouped_frames(video, FRAMES), 77)
     model = Runner(ACG_SPEC, metrics="psnr", grading_groups=True)
     assert model.takes_groups() and not Runner(ACG_SPEC, metrics="psnr", iterative_groups=True).takes_groups()
     device = torch.device("cuda", torch.cuda.current_device())
@@ -383,8 +352,8 @@ def test_cli_grading_groups(tmp_path):
         assert a.dtype == np.uint8 and a.shape == (H, W, 3) and np.array_equal(a, b), f
     # whole groups, the second one ragged: the per-frame route on the frames the groups hold
     video = SyntheticStereoVideoU8(FRAMES, H, W, group=GROUP)
-    want8, _ = per_frame_route(grouped_frames(video), 123)
-    _, want_psnr = per_frame_route(grouped_frames(video), 321)
+    want8, _ = per_frame_route(ACG_SPEC, grouped_frames(video, FRAMES), 123)
+    _, want_psnr = per_frame_route(ACG_SPEC, grouped_frames(video, FRAMES), 321)
     assert psnr_close(groups3[:, 0], want_psnr[:, 1], H * W)
     for f in range(FRAMES):
         assert np.array_equal(np.load(tmp_path / "groups3" / ("%06d.npy" % f)), want8[f]), f

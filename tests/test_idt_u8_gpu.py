@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import iterative as oit
+from tests.u8_common import ULP, dev, grouped_frames, image, per_frame_route, psnr_close, rotations, same
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -21,36 +22,12 @@ torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = os.path.join(ROOT, "color-transfer_amd", "configs")
 IDT_SPEC = "methods.iterative.iterative_distribution_transfer"
-ULP = 2.0 ** -53
 PROBES = ("hist", "lut", "par", "binidx")
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, copy=True)).cuda()
 
 
 def frames(n, batch, seed):
     """seeded random bytes [batch, n, 1, 3]"""
     return np.random.default_rng(100003 * seed + 17 * n + batch).integers(0, 256, (batch, n, 1, 3), dtype=np.uint8)
-
-
-def rotations(n_iter, seed, batch=None):
-    np.random.seed(seed)
-    return oit.draw_rotations(n_iter) if batch is None else np.stack([oit.draw_rotations(n_iter) for _ in range(batch)])
-
-
-def image(k, f32):
-    """the float image the bytes stand for"""
-    return k.astype(np.float32) / np.float32(255) if f32 else k / 255.0
-
-
-def bits(t):
-    """an integer view: equal bits, a NaN for the same NaN"""
-    return t.view({torch.float64: torch.int64, torch.float32: torch.int32}.get(t.dtype, t.dtype))
-
-
-def same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and bool(torch.equal(bits(a), bits(b)))
 
 
 def same_probes(d, want):
@@ -321,46 +298,11 @@ def test_methods_route():
 H, W, FRAMES, GROUP = 24, 40, 5, 3               # two groups, the second one ragged
 
 
-def grouped_frames(video):
-    """the frames as the grouped route sees them (a group's content is defined by its first frame): [(target, reference, gt)] uint8 HWC"""
-    out = []
-    for first in range(0, FRAMES, video.group):
-        chunk = video.host_chunk(first)
-        out += [tuple(chunk[i, j] for i in range(3)) for j in range(min(video.group, FRAMES - first))]
-    return out
-
-
-def per_frame_route(triples, seed, skip=0):
-    """the per-frame Runner (forward, clamp, pack_u8; test_step) on a seeded np.random, for uint8 HWC (target, reference, gt)
-    triples made float32 CHW as the datasets make them: (bytes [n,H,W,3], rows [n,2] of (mse, PSNR) as methods.psnr computes them);
-    skip: that many frames' draws discarded first"""
-    import ct_hip
-    import methods.iterative as it
-    from methods import Runner
-    model = Runner(IDT_SPEC, metrics="psnr")
-    assert not model.takes_groups()
-    batches = [{k: (x.permute(2, 0, 1).float() / 255)[None].cuda() for k, x in zip(("target", "reference", "gt"), tr)} for tr in triples]
-    np.random.seed(seed)
-    it.draw_group_rotations(skip)
-    frames_u8 = [ct_hip.pack_u8(model(b).clamp(0, 1).contiguous(), "chw")[0].cpu().numpy() for b in batches]
-    np.random.seed(seed)
-    it.draw_group_rotations(skip)
-    rows = [ct_hip.frame_psnr(model(b).clamp(0, 1).float().contiguous(), b["gt"].float().contiguous())[0].cpu().numpy() for b in batches]
-    return np.stack(frames_u8), np.stack(rows)
-
-
-def psnr_close(got, want, n):
-    """PSNR values of mse values that agree within 3 n 2^-53 relative: d(10 log10(1 / mse)) = 10 / ln 10 * d(mse) / mse, plus the
-    1e-12 relative that test_mk_psnr allows for the logarithm itself"""
-    got, want = np.asarray(got), np.asarray(want)
-    return bool((np.abs(got - want) <= 10 / np.log(10) * 3 * n * ULP + 1e-12 * np.maximum(1.0, np.abs(want))).all())
-
-
 def test_runner_groups():
     from methods import Runner
     from utils.data import SyntheticStereoVideoU8, prefetch_groups
     video = SyntheticStereoVideoU8(FRAMES, H, W, group=FRAMES, pool=2)
-    want8, want_psnr = per_frame_route(grouped_frames(video), 77)
+    want8, want_psnr = per_frame_route(IDT_SPEC, grouped_frames(video, FRAMES), 77)
     model = Runner(IDT_SPEC, metrics="psnr", iterative_groups=True)
     assert model.takes_groups() and not Runner(IDT_SPEC, metrics="psnr", byte_groups=True).takes_groups()
     device = torch.device("cuda", torch.cuda.current_device())
@@ -400,7 +342,7 @@ def test_cli_predict_iterative_groups(tmp_path):
     timing = {}
     assert cli.main(args + ["--model.iterative_groups", "true", "--output", str(tmp_path / "groups")], timing=timing) == FRAMES
     assert timing["grouped"] is True and timing["frames_per_call"] == GROUP
-    want8, _ = per_frame_route(grouped_frames(video), 123, skip=warm)                # the per-frame route on the same frames
+    want8, _ = per_frame_route(IDT_SPEC, grouped_frames(video, FRAMES), 123, skip=warm)                # the per-frame route on the same frames
     for f in range(FRAMES):
         got = np.load(tmp_path / "groups" / ("%06d.npy" % f))
         assert got.dtype == np.uint8 and np.array_equal(got, want8[f]), f
@@ -409,7 +351,7 @@ def test_cli_predict_iterative_groups(tmp_path):
     timing = {}
     assert cli.main(args + ["--output", str(tmp_path / "plain")], timing=timing) == FRAMES
     assert timing["grouped"] is False
-    plain8, _ = per_frame_route([tuple(video.host_chunk(f)[i, 0] for i in range(3)) for f in range(FRAMES)], 123)
+    plain8, _ = per_frame_route(IDT_SPEC, [tuple(video.host_chunk(f)[i, 0] for i in range(3)) for f in range(FRAMES)], 123)
     for f in range(FRAMES):
         got = np.load(tmp_path / "plain" / ("%06d.npy" % f))
         assert got.dtype == np.uint8 and np.array_equal(got, plain8[f]), f
@@ -420,7 +362,7 @@ def test_cli_test_iterative_groups():
     from utils.data import SyntheticStereoVideoU8
     np.random.seed(321)
     grouped = cli.main(cli_args("test") + ["--model.iterative_groups", "true"])
-    _, want = per_frame_route(grouped_frames(SyntheticStereoVideoU8(FRAMES, H, W, group=GROUP)), 321)
+    _, want = per_frame_route(IDT_SPEC, grouped_frames(SyntheticStereoVideoU8(FRAMES, H, W, group=GROUP), FRAMES), 321)
     assert tuple(grouped.shape) == (FRAMES, 4)
     assert psnr_close(grouped[:, 0].cpu().numpy(), want[:, 1], H * W)
     assert bool(torch.isnan(grouped[:, 1:]).all())

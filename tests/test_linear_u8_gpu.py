@@ -20,17 +20,13 @@ import pytest
 
 from tests.linear_u8_common import (BATCHES, DECOMPS, MAX_TIE_SHARE, MK_SPEC, PAIRS, PIXELS, XIAO_SPEC, exact_moments, fixture, frames,
                                     rel_error, tie_mask)
+from tests.u8_common import ULP, dev
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = os.path.join(ROOT, "color-transfer_amd", "configs")
-ULP = 2.0 ** -53
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, copy=True)).cuda()
 
 
 def same_bits(got, want):
