@@ -326,6 +326,19 @@ size_t ct_fsim_workspace_bytes(int batch, int h, int w) {
     return ct::fsim_layout(nullptr, 2 * batch, hp * wp).total;
 }
 
+// byte offsets of the iq [2 batch][2][P], grad [2 batch][P], pc [2 batch][P] and thr [2 batch][4] regions inside the workspace
+// of ct_frame_fsim_f32(batch, h, w): what the call leaves there (host only; for tests that read the stages)
+int ct_fsim_stage_offsets(int batch, int h, int w, size_t out[4]) {
+    if (!out || ct_fsim_workspace_bytes(batch, h, w) == 0) return CT_E_BADARG;
+    const int f = ct::fsim_factor(h, w);
+    const ct::FsimLayout l = ct::fsim_layout(nullptr, 2 * batch, (h / f) * (w / f));
+    out[0] = reinterpret_cast<size_t>(l.iq);
+    out[1] = reinterpret_cast<size_t>(l.grad);
+    out[2] = reinterpret_cast<size_t>(l.pc);
+    out[3] = reinterpret_cast<size_t>(l.thr);
+    return CT_OK;
+}
+
 // filters: [16][hp*wp] float32 (orientation-major), consts: [4][3] float64; both on the device, valid for every frame of this size
 int ct_fsim_setup_f32(int h, int w, float *filters, double *consts, void *ws, size_t ws_bytes, void *stream) {
     if (!filters || !consts || !ws || h < 1 || w < 1 || (reinterpret_cast<uintptr_t>(ws) & 255)) return CT_E_BADARG;

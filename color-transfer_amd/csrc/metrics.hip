@@ -14,7 +14,8 @@
 // down-sampled inputs (plus a 5-pixel halo) into LDS straight from the full-resolution NCHW planes, runs the separable
 // 11-tap Gaussian (rows into LDS, then columns) for all 5 / 11 moment maps at once, evaluates the per-pixel formula and
 // reduces it to one float64 partial sum; a finishing kernel adds the partials in a fixed order (deterministic).  float32
-// arithmetic like the reference's torch code, float64 sums.
+// arithmetic, float64 sums; unlike the reference's torch code the second moments are taken about a pivot pixel of the tile, so
+// that flat and saturated frames stay on the float64 value (the reference's float32 run leaves it by 3e-4 there: DESIGN.md 4.6).
 #include "ct_color.h"
 #include "ct_common.h"
 #include "ct_metrics.h"
@@ -55,6 +56,11 @@ __global__ __launch_bounds__(kBlock) void ssim_tile_kernel(const float *__restri
     const int Ho = Hp - kHalo, Wo = Wp - kHalo;
     gauss_weights(w, 1.5f);
     const float inv = 1.0f / (float)(f * f);
+    // moments about a pivot of the tile (a frame pixel near its middle): variances and the covariance do not depend on it, and
+    // E[x^2] - mu^2 no longer cancels from O(1) on a flat or saturated frame, where the float32 rounding of the sums over
+    // c2 = 9e-4 put SSIM 2.6e-4 above 1.  Tile entries past the frame stay 0 and feed masked outputs only.
+    const size_t pivot = (size_t)((oy + min(kSsTH / 2 + 5, Hp - 1 - oy)) * f) * W + (size_t)((ox + min(kSsTW / 2 + 5, Wp - 1 - ox)) * f);
+    const float pvx = pa[pivot], pvy = pb[pivot];
     for (int i = threadIdx.x; i < (kSsTH + kHalo) * (kSsTW + kHalo); i += kBlock) {
         const int r = i / (kSsTW + kHalo), c = i % (kSsTW + kHalo);
         const int py = oy + r, px = ox + c;
@@ -65,7 +71,7 @@ __global__ __launch_bounds__(kBlock) void ssim_tile_kernel(const float *__restri
                     const size_t o = (size_t)(py * f + dy) * W + (px * f + dx);
                     vx += pa[o]; vy += pb[o];
                 }
-            vx *= inv; vy *= inv;                      // F.avg_pool2d(kernel_size = f)
+            vx = vx * inv - pvx; vy = vy * inv - pvy;  // F.avg_pool2d(kernel_size = f), about the pivot
         }
         sx[r][c] = vx; sy[r][c] = vy;
     }
@@ -93,8 +99,9 @@ __global__ __launch_bounds__(kBlock) void ssim_tile_kernel(const float *__restri
                 for (int q = 0; q < 5; ++q) m[q] = fmaf(w[k], hb[q][r + k][c], m[q]);
             }
             const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
-            const float mxx = m[0] * m[0], myy = m[1] * m[1], mxy = m[0] * m[1];
-            const float sxx = m[2] - mxx, syy = m[3] - myy, sxy = m[4] - mxy;
+            const float mx = m[0] + pvx, my = m[1] + pvy;                    // the window means; m[] are about the pivots
+            const float mxx = mx * mx, myy = my * my, mxy = mx * my;
+            const float sxx = m[2] - m[0] * m[0], syy = m[3] - m[1] * m[1], sxy = m[4] - m[0] * m[1];
             const float cs = (2.0f * sxy + c2) / (sxx + syy + c2);
             acc += (double)((2.0f * mxy + c1) / (mxx + myy + c1) * cs);
         }
@@ -148,6 +155,10 @@ __global__ __launch_bounds__(kBlock) void icid_tile_kernel(const float *__restri
         for (int q = 0; q < 5; ++q) base[q][r][c] = v[q];
     }
     __syncthreads();
+    // L and C moments about pivots of the tile (a map pixel near its middle): with L near 100 the sums of L^2 carry a float32
+    // rounding of 1e-3 against the maps' constant 10, which on a saturated frame put |sL12| above sL1 sL2 and iCID below 0
+    const int pr = 5 + min(kIcTH / 2, h - 1 - oy), pc = 5 + min(kIcTW / 2, w_ - 1 - ox);
+    const float p0 = base[0][pr][pc], p1 = base[1][pr][pc], p2 = base[2][pr][pc], p3 = base[3][pr][pc];
     for (int i = threadIdx.x; i < (kIcTH + kHalo) * kIcTW; i += kBlock) {
         const int r = i / kIcTW, c = i % kIcTW;
         float m[11];
@@ -155,7 +166,8 @@ __global__ __launch_bounds__(kBlock) void icid_tile_kernel(const float *__restri
         for (int q = 0; q < 11; ++q) m[q] = 0.f;
 #pragma unroll
         for (int k = 0; k < kTaps; ++k) {
-            const float g = w[k], L1 = base[0][r][c + k], C1 = base[1][r][c + k], L2 = base[2][r][c + k], C2 = base[3][r][c + k];
+            const float g = w[k], L1 = base[0][r][c + k] - p0, C1 = base[1][r][c + k] - p1, L2 = base[2][r][c + k] - p2,
+                        C2 = base[3][r][c + k] - p3;
             m[0] = fmaf(g, L1, m[0]); m[1] = fmaf(g, C1, m[1]); m[2] = fmaf(g, L2, m[2]); m[3] = fmaf(g, C2, m[3]);
             m[4] = fmaf(g, L1 * L1, m[4]); m[5] = fmaf(g, L2 * L2, m[5]); m[6] = fmaf(g, C1 * C1, m[6]); m[7] = fmaf(g, C2 * C2, m[7]);
             m[8] = fmaf(g, base[4][r][c + k], m[8]); m[9] = fmaf(g, L1 * L2, m[9]); m[10] = fmaf(g, C1 * C2, m[10]);
@@ -176,11 +188,12 @@ __global__ __launch_bounds__(kBlock) void icid_tile_kernel(const float *__restri
 #pragma unroll
                 for (int q = 0; q < 11; ++q) m[q] = fmaf(w[k], hb[q][r + k][c], m[q]);
             }
-            const float muL1 = m[0], muC1 = m[1], muL2 = m[2], muC2 = m[3];
+            const float muL1 = m[0], muC1 = m[1], muL2 = m[2], muC2 = m[3];      // about the pivots, like m[4..7], m[9], m[10]
             const float sL1q = fmaxf(m[4] - muL1 * muL1, 0.f), sL2q = fmaxf(m[5] - muL2 * muL2, 0.f);
             const float sC1q = fmaxf(m[6] - muC1 * muC1, 0.f), sC2q = fmaxf(m[7] - muC2 * muC2, 0.f);
             const float sL1 = sqrtf(sL1q), sL2 = sqrtf(sL2q), sC1 = sqrtf(sC1q), sC2 = sqrtf(sC2q);
-            const float dLq = (muL1 - muL2) * (muL1 - muL2), dCq = (muC1 - muC2) * (muC1 - muC2), dHq = m[8] * m[8];
+            const float dL = (muL1 - muL2) + (p0 - p2), dC = (muC1 - muC2) + (p1 - p3);
+            const float dLq = dL * dL, dCq = dC * dC, dHq = m[8] * m[8];
             const float sL12 = m[9] - muL1 * muL2, sC12 = m[10] - muC1 * muC2;
             // perceptual intent: weights (0.002, 10, 10, 0.002, 0.002, 10, 10), exponents (1, 1, 3, 1, 1, 1, 1)
             const float m1 = 1.f / (0.002f * dLq + 1.f);

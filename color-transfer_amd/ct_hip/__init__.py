@@ -20,7 +20,7 @@ from .linear import (CT_LAB_EXACT, CT_LAB_TABLE, affine3x3, lab_mode, lab_stats,
                      reinhard_apply, reinhard_persist, reinhard_persist_supported, reinhard_psnr, reinhard_takes_persist,
                      rgb_meancov, set_lab_mode, upload_records)
 from .metrics import (CT_WS_FSIM, DISTORTIONS, distort_u8, fft2d_, frame_fsim, frame_icid, frame_psnr, frame_ssim, regrain,
-                      _fsim_tables)
+                      _fsim_stages, _fsim_tables)
 from .idt import IdtDebug, idt, idt_u8
 from .grading import acg_u8, regrain_u8
 from .resize_pack import CT_PACK_CHW, CT_PACK_HWC, PACK_LAYOUTS, bicubic_resize, bilinear_resize, pack_u8, resize_geometry

@@ -17,6 +17,7 @@ SIGNATURES.update({
     "ct_fft2d_c2c_f32": (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
     "ct_fsim_pooled_size": (_c_int, [_c_int, _c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "ct_fsim_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
+    "ct_fsim_stage_offsets": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
     "ct_fsim_setup_f32": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
     "ct_frame_fsim_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
 })
@@ -30,6 +31,8 @@ def frame_psnr(a, b):
     B = a.shape[0]
     n = a.numel() // max(B, 1)
     out = torch.empty((B, 2), dtype=torch.float64, device=a.device)
+    if B == 0:
+        return out
     ws = workspace(CT_WS_LAB_STATS, n, B, a.device)
     check(lib().ct_frame_psnr_f32(_ptr(a), _ptr(b), n, B, _ptr(out), _ptr(ws), ws.numel(), _stream()))
     return out
@@ -81,6 +84,8 @@ def _frame_metric(name, a, b):
         raise CtHipError("%s needs two float32 [B,3,H,W] tensors of one shape" % name)
     B, _, h, w = a.shape
     out = torch.empty((B,), dtype=torch.float64, device=a.device)
+    if B == 0:                                     # an empty tensor has a null data pointer, which the library refuses
+        return out
     ws = workspace(CT_WS_LAB_STATS, 0, B, a.device, need=lib().ct_metric_workspace_bytes(h, w, B))
     check(getattr(lib(), name)(_ptr(a), _ptr(b), h, w, B, _ptr(out), _ptr(ws), ws.numel(), _stream()))
     return out
@@ -145,3 +150,27 @@ def frame_fsim(a, b):
             _fsim_tables[key] = tab
     check(lib().ct_frame_fsim_f32(_ptr(a), _ptr(b), _ptr(out), B, h, w, _ptr(tab[0]), _ptr(tab[1]), _ptr(ws), ws.numel(), _stream()))
     return out
+
+
+def _fsim_stages(a, b):
+    """frame_fsim(a, b) and clones of what it leaves in its workspace (tests read the stages behind the weighted mean): a dict
+    with "score" [B] float64 and float32 tensors with image index 2 * pair + (0: a, 1: b) -- "iq" [2B, 2, hp, wp], "grad" and
+    "pc" [2B, hp, wp], "thr" [2B, 4]."""
+    out = frame_fsim(a, b)
+    B, _, h, w = a.shape
+    if B == 0:
+        raise CtHipError("_fsim_stages needs at least one pair")
+    hp, wp = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().ct_fsim_pooled_size(h, w, ctypes.byref(hp), ctypes.byref(wp)))
+    hp, wp = hp.value, wp.value
+    off = (_c_sz * 4)()
+    check(lib().ct_fsim_stage_offsets(B, h, w, off))
+    ws = _fsim_ws(a.device, B, h, w)                 # the same (device, stream) buffer and alignment frame_fsim just used
+
+    def region(o, *shape):
+        n = 1
+        for v in shape:
+            n *= v
+        return ws[o:o + 4 * n].view(torch.float32).view(*shape).clone()
+    return {"score": out, "iq": region(off[0], 2 * B, 2, hp, wp), "grad": region(off[1], 2 * B, hp, wp),
+            "pc": region(off[2], 2 * B, hp, wp), "thr": region(off[3], 2 * B, 4)}

@@ -639,6 +639,10 @@ int ct_fb_check_f32(const float *fwd, const float *bwd, const float *warped_bwd,
 int ct_fft2d_c2c_f32(void *data, int hp, int wp, int planes, int inverse, void *stream);
 int ct_fsim_pooled_size(int h, int w, int *hp, int *wp);
 size_t ct_fsim_workspace_bytes(int batch, int h, int w);
+/* host only: byte offsets, inside the workspace of ct_frame_fsim_f32(batch, h, w), of what the call leaves there -- out[0] the I / Q
+ *   planes [2 batch][2][hp*wp], out[1] the Scharr magnitude [2 batch][hp*wp], out[2] the phase-congruency map [2 batch][hp*wp],
+ *   out[3] the noise thresholds [2 batch][4], all float32, image index 2 * pair + (0: a, 1: b)                           */
+int ct_fsim_stage_offsets(int batch, int h, int w, size_t out[4]);
 int ct_fsim_setup_f32(int h, int w, float *filters, double *consts, void *ws, size_t ws_bytes, void *stream);
 int ct_frame_fsim_f32(const float *a, const float *b, double *out, int batch, int h, int w, const float *filters,
                       const double *consts, void *ws, size_t ws_bytes, void *stream);

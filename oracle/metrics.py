@@ -41,9 +41,10 @@ def _gaussian_2d(size, sigma, dtype):
     return g / g.sum()
 
 
-def ssim(x, y, kernel_size=11, kernel_sigma=1.5, k1=0.01, k2=0.03, downsample=True):
-    """piq.ssim(x, y, data_range=1., reduction='none') -> [B]"""
-    x, y = x.double(), y.double()
+def ssim(x, y, kernel_size=11, kernel_sigma=1.5, k1=0.01, k2=0.03, downsample=True, dtype=torch.float64, return_map=False):
+    """piq.ssim(x, y, data_range=1., reduction='none') -> [B]; dtype=torch.float32: the reference as it runs; return_map: the
+    per-pixel map [B, C, Ho, Wo] whose mean the value is"""
+    x, y = x.to(dtype), y.to(dtype)
     f = metric_factor(*x.shape[-2:])
     if f > 1 and downsample:
         x, y = F.avg_pool2d(x, kernel_size=f), F.avg_pool2d(y, kernel_size=f)
@@ -57,6 +58,8 @@ def ssim(x, y, kernel_size=11, kernel_sigma=1.5, k1=0.01, k2=0.03, downsample=Tr
     sigma_xy = F.conv2d(x * y, kernel, groups=c) - mu_xy
     cs = (2.0 * sigma_xy + c2) / (sigma_xx + sigma_yy + c2)
     ss = (2.0 * mu_xy + c1) / (mu_xx + mu_yy + c1) * cs
+    if return_map:
+        return ss
     return ss.mean(dim=(-1, -2)).mean(dim=1)
 
 
@@ -88,10 +91,11 @@ def gaussian_blur(img, kernel_size, sigma):                        # torchvision
     return x.reshape(shape)
 
 
-def icid(img1, img2):
+def icid(img1, img2, dtype=torch.float64, return_map=False):
     """utils/icid.py:28-152 with intent="perceptual", omit_maps67=False, downsampling=True -> scalar (mean over the batch and
-    positions, like the reference); use a batch of one for a per-frame value"""
-    img1, img2 = img1.double(), img2.double()
+    positions, like the reference); use a batch of one for a per-frame value.  dtype=torch.float32: the reference as it runs;
+    return_map: the product of the seven maps [B, h, w] (the value is 1 - its mean)"""
+    img1, img2 = img1.to(dtype), img2.to(dtype)
     # the reference builds its weights with torch.tensor([...]) -> float32 (0.002 becomes 0.00200000009499...), whatever
     # the dtype of the images (utils/icid.py:44)
     w = [float(v) for v in torch.tensor([0.002, 10, 10, 0.002, 0.002, 10, 10], dtype=torch.float32)]
@@ -123,16 +127,17 @@ def icid(img1, img2):
     prod = maps[0]
     for m in maps[1:]:
         prod = prod * m
+    if return_map:
+        return prod
     return 1 - prod.mean()
 
 
-
 # ---- FSIM (piq/fsim.py) -------------------------------------------------------------------------------------------------
-def _meshgrid(size):                                               # piq.functional.get_meshgrid
+def _meshgrid(size, dtype=torch.float64):                          # piq.functional.get_meshgrid
     def axis(n):
         if n % 2:
-            return torch.arange(-(n - 1) / 2, n / 2, dtype=torch.float64) / (n - 1)
-        return torch.arange(-n / 2, n / 2, dtype=torch.float64) / n
+            return torch.arange(-(n - 1) / 2, n / 2, dtype=dtype) / (n - 1)
+        return torch.arange(-n / 2, n / 2, dtype=dtype) / n
     return torch.meshgrid(axis(size[0]), axis(size[1]), indexing="ij")
 
 
@@ -140,16 +145,16 @@ def _ifftshift(x):                                                 # piq.functio
     return torch.roll(x, shifts=[-(n // 2) for n in x.shape], dims=list(range(x.dim())))
 
 
-def fsim_filters(h, w, scales=4, orientations=4, min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2):
+def fsim_filters(h, w, scales=4, orientations=4, min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2, dtype=torch.float64):
     """[orientations * scales, h, w] log-Gabor filter bank of piq's _construct_filters (orientation-major)"""
     theta_sigma = math.pi / (orientations * delta_theta)
-    gx, gy = _meshgrid((h, w))
+    gx, gy = _meshgrid((h, w), dtype)
     radius = torch.sqrt(gx ** 2 + gy ** 2)
     theta = torch.atan2(-gy, gx)
     radius, theta = _ifftshift(radius), _ifftshift(theta)
     radius[0, 0] = 1
     sintheta, costheta = torch.sin(theta), torch.cos(theta)
-    lx, ly = _meshgrid((h, w))
+    lx, ly = _meshgrid((h, w), dtype)
     lp = _ifftshift(1.0 / (1.0 + (torch.sqrt(lx ** 2 + ly ** 2) / 0.45) ** (2 * 15)))        # _lowpassfilter(cutoff=.45, n=15)
     log_gabor = []
     for s_ in range(scales):
@@ -168,10 +173,13 @@ def fsim_filters(h, w, scales=4, orientations=4, min_length=6, mult=2, sigma_f=0
     return spread.repeat_interleave(scales, dim=0) * log_gabor.repeat(orientations, 1, 1)
 
 
-def _phase_congruency(x, scales=4, orientations=4, k=2.0, eps=torch.finfo(torch.float32).eps):
-    """x: [N, 1, H, W] float64 -> [N, 1, H, W]; piq's _phase_congruency (EPS is float32's there: the reference runs in float32)"""
+def _phase_congruency(x, scales=4, orientations=4, k=2.0, eps=torch.finfo(torch.float32).eps, dtype=torch.float64,
+                      return_threshold=False):
+    """x: [N, 1, H, W] -> [N, 1, H, W]; piq's _phase_congruency (EPS is float32's there: the reference runs in float32), computed
+    in `dtype`; return_threshold: also the noise threshold T per image and orientation [N, orientations]"""
+    x = x.to(dtype)
     n, _, h, w = x.shape
-    filters = fsim_filters(h, w, scales, orientations).unsqueeze(0)
+    filters = fsim_filters(h, w, scales, orientations, dtype=dtype).unsqueeze(0)
     imagefft = torch.fft.fft2(x)
     filters_ifft = torch.fft.ifft2(filters).real * math.sqrt(h * w)
     eo = torch.fft.ifft2(imagefft * filters).view(n, orientations, scales, h, w)
@@ -196,27 +204,37 @@ def _phase_congruency(x, scales=4, orientations=4, k=2.0, eps=torch.finfo(torch.
     tau = torch.sqrt(noise_energy2 / 2)
     t = (tau * math.sqrt(math.pi / 2) + k * torch.sqrt((2 - math.pi / 2) * tau ** 2)) / 1.7
     energy = torch.max(energy - t, torch.zeros_like(t))
-    return ((energy.sum(dim=[1, 2]) + eps) / (an.sum(dim=[1, 2]) + eps)).unsqueeze(1)
+    pc = ((energy.sum(dim=[1, 2]) + eps) / (an.sum(dim=[1, 2]) + eps)).unsqueeze(1)
+    if return_threshold:
+        return pc, t.reshape(n, orientations)
+    return pc
 
 
 def _similarity(a, b, c):                                          # piq.functional.similarity_map
     return (2.0 * a * b + c) / (a ** 2 + b ** 2 + c)
 
 
-def fsim(x, y):
-    """piq.fsim(x, y, reduction='none'-like: one value per sample), data_range 1, chromatic"""
-    x, y = x.double() * 255, y.double() * 255
-    f = metric_factor(x.shape[-2], x.shape[-1])
-    x, y = F.avg_pool2d(x, f), F.avg_pool2d(y, f)
-    m = torch.tensor([[0.299, 0.587, 0.114], [0.5959, -0.2746, -0.3213], [0.2115, -0.5227, 0.3112]], dtype=torch.float64)   # rgb2yiq
-    xq, yq = torch.einsum("kc,nchw->nkhw", m, x), torch.einsum("kc,nchw->nkhw", m, y)
-    xl, yl = xq[:, :1], yq[:, :1]
-    pc_x, pc_y = _phase_congruency(xl), _phase_congruency(yl)
-    sch = torch.tensor([[-3.0, 0.0, 3.0], [-10.0, 0.0, 10.0], [-3.0, 0.0, 3.0]], dtype=torch.float64) / 16
-    kern = torch.stack([sch, sch.t()]).unsqueeze(1)
+def _fsim_yiq(x, dtype):
+    """x255, piq's average pooling, rgb2yiq: [N, 3, H, W] in 0..1 -> [N, 3, hp, wp] (Y, I, Q) in `dtype`"""
+    x = x.to(dtype) * 255
+    x = F.avg_pool2d(x, metric_factor(x.shape[-2], x.shape[-1]))
+    m = torch.tensor([[0.299, 0.587, 0.114], [0.5959, -0.2746, -0.3213], [0.2115, -0.5227, 0.3112]], dtype=dtype)   # rgb2yiq
+    return torch.einsum("kc,nchw->nkhw", m, x)
 
-    def grad(z):
-        return torch.sqrt((F.conv2d(z, kern, padding=1) ** 2).sum(dim=1, keepdim=True))
+
+def _scharr_magnitude(z):
+    sch = torch.tensor([[-3.0, 0.0, 3.0], [-10.0, 0.0, 10.0], [-3.0, 0.0, 3.0]], dtype=z.dtype) / 16
+    kern = torch.stack([sch, sch.t()]).unsqueeze(1)
+    return torch.sqrt((F.conv2d(z, kern, padding=1) ** 2).sum(dim=1, keepdim=True))
+
+
+def fsim(x, y, dtype=torch.float64):
+    """piq.fsim(x, y, reduction='none'-like: one value per sample), data_range 1, chromatic; dtype=torch.float32: the reference
+    as it runs"""
+    xq, yq = _fsim_yiq(x, dtype), _fsim_yiq(y, dtype)
+    xl, yl = xq[:, :1], yq[:, :1]
+    pc_x, pc_y = _phase_congruency(xl, dtype=dtype), _phase_congruency(yl, dtype=dtype)
+    grad = _scharr_magnitude
     pc = _similarity(pc_x, pc_y, 0.85)
     gm = _similarity(grad(xl), grad(yl), 160.0)
     pc_max = torch.where(pc_x > pc_y, pc_x, pc_y)
@@ -224,3 +242,11 @@ def fsim(x, y):
     s_i, s_q = _similarity(xq[:, 1:2], yq[:, 1:2], 200.0), _similarity(xq[:, 2:], yq[:, 2:], 200.0)
     score = score * torch.abs(s_i * s_q) ** 0.03
     return score.sum(dim=[1, 2, 3]) / pc_max.sum(dim=[1, 2, 3])
+
+
+def fsim_stages(x, dtype=torch.float64):
+    """What fsim computes of ONE batch of frames [N, 3, H, W] in 0..1 before the similarity maps: the pooled planes "y", "i", "q",
+    the Scharr magnitude "grad", the phase-congruency map "pc" (each [N, hp, wp]) and the four noise thresholds "t" [N, 4]"""
+    q = _fsim_yiq(x, dtype)
+    pc, t = _phase_congruency(q[:, :1], dtype=dtype, return_threshold=True)
+    return {"y": q[:, 0], "i": q[:, 1], "q": q[:, 2], "grad": _scharr_magnitude(q[:, :1])[:, 0], "pc": pc[:, 0], "t": t}
