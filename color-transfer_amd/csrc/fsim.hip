@@ -12,7 +12,10 @@
 // smallest-scale energy per orientation for the noise threshold, the phase-congruency map, the similarity / score
 // reduction (float64 partial sums, fixed order).  The filter bank and its three noise constants per orientation depend on
 // the pooled size only: ct_fsim_setup_f32 builds them once on the device.  float32 arithmetic like the reference.
+// Only fsim_prep_kernel reads the frames, through the frame sources of ct_frame_src.h: planar float32 (ct_frame_fsim_f32) or a
+// frame group's float32 HWC result and uint8 HWC ground truth (ct_frame_fsim_hwc_u8), bitwise the first on the converted tensors.
 #include "ct_common.h"
+#include "ct_frame_src.h"
 
 namespace ct {
 
@@ -122,24 +125,38 @@ __global__ __launch_bounds__(256) void fsim_consts_kernel(const float *__restric
 }
 
 // ---- per call ------------------------------------------------------------------------------------------------------------
-// average pooling + x255 + YIQ; image index = 2 * pair + (0: a, 1: b)
-__global__ __launch_bounds__(256) void fsim_prep_kernel(const float *__restrict__ a, const float *__restrict__ b, int H, int W, int f, int hp,
-                                                        int wp, float2 *__restrict__ lum, float *__restrict__ iq) {
+// c[ch] = avg_pool(255 x) of one frame source (ct_frame_src.h) at pooled pixel (py, px): per channel the f x f values added row by row
+template <class S> __device__ __forceinline__ void fsim_pool3(const S &src, int W, int f, int py, int px, float (&c)[3]) {
+    const float inv = 1.0f / (float)(f * f);
+    float s[3] = {0.f, 0.f, 0.f};
+    for (int dy = 0; dy < f; ++dy)
+        for (int dx = 0; dx < f; ++dx) {
+            float v[3];
+            src.at3((size_t)(py * f + dy) * W + px * f + dx, v);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) s[ch] += v[ch] * 255.0f;
+        }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) c[ch] = s[ch] * inv;
+}
+
+// average pooling + x255 + YIQ; image index = 2 * pair + (0: a through SA, 1: b through SB)
+template <class SA, class SB>
+__global__ __launch_bounds__(256) void fsim_prep_kernel(const typename SA::elem *__restrict__ a, const typename SB::elem *__restrict__ b, int H, int W,
+                                                        int f, int hp, int wp, float2 *__restrict__ lum, float *__restrict__ iq) {
+    __shared__ float tab[SA::kTable || SB::kTable ? 256 : 1];
+    if constexpr (SA::kTable || SB::kTable) {
+        fill_u8_table_f32(tab);
+        __syncthreads();
+    }
     const int P = hp * wp;
     const int p = blockIdx.x * 256 + threadIdx.x;
     const int img = blockIdx.y;
     if (p >= P) return;
-    const float *src = ((img & 1) ? b : a) + (size_t)(img >> 1) * 3 * H * W;
     const int py = p / wp, px = p - py * wp;
     float c[3];
-    const float inv = 1.0f / (float)(f * f);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        float s = 0.f;
-        for (int dy = 0; dy < f; ++dy)
-            for (int dx = 0; dx < f; ++dx) s += src[(size_t)ch * H * W + (size_t)(py * f + dy) * W + px * f + dx] * 255.0f;
-        c[ch] = s * inv;
-    }
+    if (img & 1) fsim_pool3(SB(b, img >> 1, H, W, tab), W, f, py, px, c);
+    else fsim_pool3(SA(a, img >> 1, H, W, tab), W, f, py, px, c);
     const float y = 0.299f * c[0] + 0.587f * c[1] + 0.114f * c[2];
     const float i = 0.5959f * c[0] - 0.2746f * c[1] - 0.3213f * c[2];
     const float q = 0.2115f * c[0] - 0.5227f * c[1] + 0.3112f * c[2];
@@ -306,6 +323,56 @@ static int fsim_factor(int h, int w) {
     return r < 1.0 ? 1 : (int)r;
 }
 
+// out[b] = piq.fsim(a[b], b[b]) for batch frames read through the frame sources SA (result) and SB (ground truth); only
+// fsim_prep_kernel touches the frames
+template <class SA, class SB>
+static int frame_fsim(const typename SA::elem *a, const typename SB::elem *b, double *out, int batch, int h, int w, const float *filters,
+                      const double *consts, void *ws, size_t ws_bytes, void *stream) {
+    if (!a || !b || !out || !filters || !consts || !ws || batch < 0 || h < 1 || w < 1 || (reinterpret_cast<uintptr_t>(ws) & 255)) return CT_E_BADARG;
+    if (batch == 0) return CT_OK;
+    const int f = fsim_factor(h, w), hp = h / f, wp = w / f, P = hp * wp, imgs = 2 * batch;
+    if (hp < 2 || wp < 2 || imgs * kFsO > 65535) return CT_E_BADARG;
+    if (!fft2d_supported(hp, wp)) return CT_E_BADARG;
+    const FsimLayout l = fsim_layout(ws, imgs, P);
+    if (ws_bytes < l.total) return CT_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 gp((P + 255) / 256, imgs);
+    const float invP = 1.0f / (float)P;
+    { const int zr = zero_async(l.hist, (size_t)imgs * kFsO * 2048 * sizeof(unsigned int), s); if (zr) return zr; }
+    hipLaunchKernelGGL((fsim_prep_kernel<SA, SB>), gp, dim3(256), 0, s, a, b, h, w, f, hp, wp, l.lum, l.iq);
+    CT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(fsim_grad_kernel, gp, dim3(256), 0, s, (const float2 *)l.lum, hp, wp, l.grad);
+    CT_CHECK_LAUNCH();
+    { const int rc = fft2d_c2c(l.lum, hp, wp, imgs, -1, s); if (rc) return rc; }
+    hipLaunchKernelGGL(fsim_apply_filters_kernel, gp, dim3(256), 0, s, (const float2 *)l.lum, filters, P, l.eo);
+    CT_CHECK_LAUNCH();
+    { const int rc = fft2d_c2c(l.eo, hp, wp, imgs * kFsK, +1, s); if (rc) return rc; }
+    // exact lower median of the scale-0 energy per (image, orientation): 11 + 11 + 10 key bits
+    const int planes = imgs * kFsO;
+    int hb = (P + 256 * 8 - 1) / (256 * 8);
+    if (hb > 64) hb = 64;
+    const int shifts[3] = {21, 10, 0}, nbits[3] = {11, 11, 10};
+    for (int pass = 0; pass < 3; ++pass) {
+        hipLaunchKernelGGL(fsim_select_hist_kernel, dim3(hb, planes), dim3(256), 0, s, (const float2 *)l.eo, P, invP, shifts[pass], nbits[pass],
+                           pass == 0 ? 1 : 0, (const unsigned int *)l.sel, l.hist);
+        CT_CHECK_LAUNCH();
+        hipLaunchKernelGGL(fsim_select_pick_kernel, dim3(planes), dim3(64), 0, s, l.hist, l.sel, nbits[pass], pass == 0 ? 1 : 0, pass == 2 ? 1 : 0,
+                           (unsigned int)((P - 1) / 2), consts, l.thr, 2.0f);
+        CT_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(fsim_pc_kernel, gp, dim3(256), 0, s, (const float2 *)l.eo, P, invP, (const float *)l.thr, l.pc);
+    CT_CHECK_LAUNCH();
+    int sb = (P + 255) / 256;
+    if (sb > kFsScoreBlocks) sb = kFsScoreBlocks;
+    hipLaunchKernelGGL(fsim_score_kernel, dim3(sb, batch), dim3(256), 0, s, (const float *)l.pc, (const float *)l.grad, (const float *)l.iq, P,
+                       l.part);
+    CT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(fsim_finish_kernel, dim3(batch), dim3(64), 0, s, (const double *)l.part, sb, out);
+    CT_CHECK_LAUNCH();
+    return CT_OK;
+}
+
+
 }  // namespace ct
 
 extern "C" {
@@ -362,48 +429,13 @@ int ct_fsim_setup_f32(int h, int w, float *filters, double *consts, void *ws, si
 // out[b] = piq.fsim(a[b], b[b]) for batch frames [batch][3][h][w] float32 in [0, 1]
 int ct_frame_fsim_f32(const float *a, const float *b, double *out, int batch, int h, int w, const float *filters, const double *consts,
                       void *ws, size_t ws_bytes, void *stream) {
-    if (!a || !b || !out || !filters || !consts || !ws || batch < 0 || h < 1 || w < 1 || (reinterpret_cast<uintptr_t>(ws) & 255)) return CT_E_BADARG;
-    if (batch == 0) return CT_OK;
-    const int f = ct::fsim_factor(h, w), hp = h / f, wp = w / f, P = hp * wp, imgs = 2 * batch;
-    if (hp < 2 || wp < 2 || imgs * ct::kFsO > 65535) return CT_E_BADARG;
-    if (!ct::fft2d_supported(hp, wp)) return CT_E_BADARG;
-    const ct::FsimLayout l = ct::fsim_layout(ws, imgs, P);
-    if (ws_bytes < l.total) return CT_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 gp((P + 255) / 256, imgs);
-    const float invP = 1.0f / (float)P;
-    { const int zr = ct::zero_async(l.hist, (size_t)imgs * ct::kFsO * 2048 * sizeof(unsigned int), s); if (zr) return zr; }
-    hipLaunchKernelGGL(ct::fsim_prep_kernel, gp, dim3(256), 0, s, a, b, h, w, f, hp, wp, l.lum, l.iq);
-    CT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ct::fsim_grad_kernel, gp, dim3(256), 0, s, (const float2 *)l.lum, hp, wp, l.grad);
-    CT_CHECK_LAUNCH();
-    { const int rc = ct::fft2d_c2c(l.lum, hp, wp, imgs, -1, s); if (rc) return rc; }
-    hipLaunchKernelGGL(ct::fsim_apply_filters_kernel, gp, dim3(256), 0, s, (const float2 *)l.lum, filters, P, l.eo);
-    CT_CHECK_LAUNCH();
-    { const int rc = ct::fft2d_c2c(l.eo, hp, wp, imgs * ct::kFsK, +1, s); if (rc) return rc; }
-    // exact lower median of the scale-0 energy per (image, orientation): 11 + 11 + 10 key bits
-    const int planes = imgs * ct::kFsO;
-    int hb = (P + 256 * 8 - 1) / (256 * 8);
-    if (hb > 64) hb = 64;
-    const int shifts[3] = {21, 10, 0}, nbits[3] = {11, 11, 10};
-    for (int pass = 0; pass < 3; ++pass) {
-        hipLaunchKernelGGL(ct::fsim_select_hist_kernel, dim3(hb, planes), dim3(256), 0, s, (const float2 *)l.eo, P, invP, shifts[pass], nbits[pass],
-                           pass == 0 ? 1 : 0, (const unsigned int *)l.sel, l.hist);
-        CT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(ct::fsim_select_pick_kernel, dim3(planes), dim3(64), 0, s, l.hist, l.sel, nbits[pass], pass == 0 ? 1 : 0, pass == 2 ? 1 : 0,
-                           (unsigned int)((P - 1) / 2), consts, l.thr, 2.0f);
-        CT_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(ct::fsim_pc_kernel, gp, dim3(256), 0, s, (const float2 *)l.eo, P, invP, (const float *)l.thr, l.pc);
-    CT_CHECK_LAUNCH();
-    int sb = (P + 255) / 256;
-    if (sb > ct::kFsScoreBlocks) sb = ct::kFsScoreBlocks;
-    hipLaunchKernelGGL(ct::fsim_score_kernel, dim3(sb, batch), dim3(256), 0, s, (const float *)l.pc, (const float *)l.grad, (const float *)l.iq, P,
-                       l.part);
-    CT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ct::fsim_finish_kernel, dim3(batch), dim3(64), 0, s, (const double *)l.part, sb, out);
-    CT_CHECK_LAUNCH();
-    return CT_OK;
+    return ct::frame_fsim<ct::PlanarF32, ct::PlanarF32>(a, b, out, batch, h, w, filters, consts, ws, ws_bytes, stream);
+}
+
+// the same from a frame group's own buffers: the result as float32 [batch][h][w][3] (clamped as it is read), the ground truth as bytes
+int ct_frame_fsim_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, double *out, int batch, int h, int w, const float *filters,
+                         const double *consts, void *ws, size_t ws_bytes, void *stream) {
+    return ct::frame_fsim<ct::ResultHwcF32, ct::GtHwcU8>(result_hwc, gt_hwc, out, batch, h, w, filters, consts, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -16,8 +16,14 @@
 // reduces it to one float64 partial sum; a finishing kernel adds the partials in a fixed order (deterministic).  float32
 // arithmetic, float64 sums; unlike the reference's torch code the second moments are taken about a pivot pixel of the tile, so
 // that flat and saturated frames stay on the float64 value (the reference's float32 run leaves it by 3e-4 there: DESIGN.md 4.6).
+//
+// Both tile kernels are templates on the frame sources of ct_frame_src.h: planar float32 (ct_frame_*_f32), or what a group of uint8
+// frames holds -- the transfer's unclamped float32 HWC result, clamped as it is read, and the uint8 HWC ground truth through a
+// (float)k / 255.0f table in LDS (ct_frame_*_hwc_u8).  One body: the second form is bitwise the first on the converted tensors
+// (DESIGN.md 4.20).
 #include "ct_color.h"
 #include "ct_common.h"
+#include "ct_frame_src.h"
 #include "ct_metrics.h"
 
 namespace ct {
@@ -40,112 +46,159 @@ __device__ __forceinline__ double block_reduce_1(double v, double *lds /* [4] */
 }
 
 // -------------------------------------------------------------------------------------------------------------------
-// SSIM.  grid = (tiles_x, tiles_y, batch * 3); a, b: [batch][3][H][W]; pooled size Hp x Wp = (H / f, W / f).
+// SSIM.  SA / SB: the frame sources of a (result) and b (ground truth), ct_frame_src.h.  Planar sources: grid = (tiles_x,
+// tiles_y, batch * 3), a workgroup owns one plane's tile.  HWC sources: grid = (tiles_x, tiles_y, batch), a workgroup takes its
+// tile's three channels from ONE pass over the pixels (12 B + 3 B contiguous per pixel) and runs the rest channel by channel
+// through the one hb buffer; its partial of channel c lands in the slot the planar workgroup of plane img * 3 + c writes, with
+// the same thread -> pixel assignment and block_sum: the same bits, and metric_finish_kernel serves both.
+// Pooled size Hp x Wp = (H / f, W / f).  Dynamic LDS: sx, sy [NC][42][42], hb [5][42][32] floats (ssim_lds_bytes).
 // -------------------------------------------------------------------------------------------------------------------
 constexpr int kSsTW = 32, kSsTH = 32;
+constexpr size_t ssim_lds_bytes(int nc) { return ((size_t)2 * nc * (kSsTH + kHalo) * (kSsTW + kHalo) + (size_t)5 * (kSsTH + kHalo) * kSsTW) * sizeof(float); }
 
-__global__ __launch_bounds__(kBlock) void ssim_tile_kernel(const float *__restrict__ a, const float *__restrict__ b, int H, int W, int f,
-                                                           int Hp, int Wp, double *__restrict__ partials) {
-    __shared__ float sx[kSsTH + kHalo][kSsTW + kHalo], sy[kSsTH + kHalo][kSsTW + kHalo];
-    __shared__ float hb[5][kSsTH + kHalo][kSsTW];
+template <class SA, class SB>
+__global__ __launch_bounds__(kBlock) void ssim_tile_kernel(const typename SA::elem *__restrict__ a, const typename SB::elem *__restrict__ b, int H, int W,
+                                                           int f, int Hp, int Wp, double *__restrict__ partials) {
+    static_assert(SA::kHwc == SB::kHwc, "both frames planar or both HWC");
+    constexpr int NC = SA::kHwc ? 3 : 1;               // channels per workgroup
+    extern __shared__ __attribute__((aligned(16))) float ss_smem[];
+    typedef float TileRow[kSsTW + kHalo];
+    typedef float HbRow[kSsTW];
+    TileRow(*sx)[kSsTH + kHalo] = reinterpret_cast<TileRow(*)[kSsTH + kHalo]>(ss_smem);
+    TileRow(*sy)[kSsTH + kHalo] = sx + NC;
+    HbRow(*hb)[kSsTH + kHalo] = reinterpret_cast<HbRow(*)[kSsTH + kHalo]>(sy + NC);
     __shared__ float w[kTaps];
+    __shared__ float tab[SA::kTable || SB::kTable ? 256 : 1];
     __shared__ double red[4];
-    const int plane = blockIdx.z;
-    const float *pa = a + (size_t)plane * H * W, *pb = b + (size_t)plane * H * W;
+    const int img = SA::kHwc ? (int)blockIdx.z : (int)blockIdx.z / 3, c0 = SA::kHwc ? 0 : (int)blockIdx.z % 3;
     const int ox = blockIdx.x * kSsTW, oy = blockIdx.y * kSsTH;
     const int Ho = Hp - kHalo, Wo = Wp - kHalo;
     gauss_weights(w, 1.5f);
+    if constexpr (SA::kTable || SB::kTable) {
+        fill_u8_table_f32(tab);
+        __syncthreads();
+    }
+    const SA pa(a, img, H, W, tab);
+    const SB pb(b, img, H, W, tab);
     const float inv = 1.0f / (float)(f * f);
     // moments about a pivot of the tile (a frame pixel near its middle): variances and the covariance do not depend on it, and
     // E[x^2] - mu^2 no longer cancels from O(1) on a flat or saturated frame, where the float32 rounding of the sums over
     // c2 = 9e-4 put SSIM 2.6e-4 above 1.  Tile entries past the frame stay 0 and feed masked outputs only.
     const size_t pivot = (size_t)((oy + min(kSsTH / 2 + 5, Hp - 1 - oy)) * f) * W + (size_t)((ox + min(kSsTW / 2 + 5, Wp - 1 - ox)) * f);
-    const float pvx = pa[pivot], pvy = pb[pivot];
+    float pvx[NC], pvy[NC];
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) { pvx[ch] = pa.at(c0 + ch, pivot); pvy[ch] = pb.at(c0 + ch, pivot); }
     for (int i = threadIdx.x; i < (kSsTH + kHalo) * (kSsTW + kHalo); i += kBlock) {
         const int r = i / (kSsTW + kHalo), c = i % (kSsTW + kHalo);
         const int py = oy + r, px = ox + c;
-        float vx = 0.f, vy = 0.f;
+        float vx[NC], vy[NC];
+#pragma unroll
+        for (int ch = 0; ch < NC; ++ch) vx[ch] = vy[ch] = 0.f;
         if (py < Hp && px < Wp) {
             for (int dy = 0; dy < f; ++dy)
                 for (int dx = 0; dx < f; ++dx) {
                     const size_t o = (size_t)(py * f + dy) * W + (px * f + dx);
-                    vx += pa[o]; vy += pb[o];
+                    if constexpr (NC == 3) {
+                        float ta[3], tb[3];
+                        pa.at3(o, ta); pb.at3(o, tb);
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch) { vx[ch] += ta[ch]; vy[ch] += tb[ch]; }
+                    } else {
+                        vx[0] += pa.at(c0, o); vy[0] += pb.at(c0, o);
+                    }
                 }
-            vx = vx * inv - pvx; vy = vy * inv - pvy;  // F.avg_pool2d(kernel_size = f), about the pivot
-        }
-        sx[r][c] = vx; sy[r][c] = vy;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < (kSsTH + kHalo) * kSsTW; i += kBlock) {
-        const int r = i / kSsTW, c = i % kSsTW;
-        float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int k = 0; k < kTaps; ++k) {
-            const float x = sx[r][c + k], y = sy[r][c + k], g = w[k];
-            m[0] = fmaf(g, x, m[0]); m[1] = fmaf(g, y, m[1]); m[2] = fmaf(g, x * x, m[2]); m[3] = fmaf(g, y * y, m[3]); m[4] = fmaf(g, x * y, m[4]);
+            for (int ch = 0; ch < NC; ++ch) { vx[ch] = vx[ch] * inv - pvx[ch]; vy[ch] = vy[ch] * inv - pvy[ch]; }  // F.avg_pool2d(kernel_size = f), about the pivot
         }
 #pragma unroll
-        for (int q = 0; q < 5; ++q) hb[q][r][c] = m[q];
+        for (int ch = 0; ch < NC; ++ch) { sx[ch][r][c] = vx[ch]; sy[ch][r][c] = vy[ch]; }
     }
     __syncthreads();
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < kSsTH * kSsTW; i += kBlock) {
-        const int r = i / kSsTW, c = i % kSsTW;
-        if (oy + r < Ho && ox + c < Wo) {
+    // channel by channel through hb: block_sum's barrier stands between a channel's column pass and the next one's row pass
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) {
+        for (int i = threadIdx.x; i < (kSsTH + kHalo) * kSsTW; i += kBlock) {
+            const int r = i / kSsTW, c = i % kSsTW;
             float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int k = 0; k < kTaps; ++k) {
-#pragma unroll
-                for (int q = 0; q < 5; ++q) m[q] = fmaf(w[k], hb[q][r + k][c], m[q]);
+                const float x = sx[ch][r][c + k], y = sy[ch][r][c + k], g = w[k];
+                m[0] = fmaf(g, x, m[0]); m[1] = fmaf(g, y, m[1]); m[2] = fmaf(g, x * x, m[2]); m[3] = fmaf(g, y * y, m[3]); m[4] = fmaf(g, x * y, m[4]);
             }
-            const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
-            const float mx = m[0] + pvx, my = m[1] + pvy;                    // the window means; m[] are about the pivots
-            const float mxx = mx * mx, myy = my * my, mxy = mx * my;
-            const float sxx = m[2] - m[0] * m[0], syy = m[3] - m[1] * m[1], sxy = m[4] - m[0] * m[1];
-            const float cs = (2.0f * sxy + c2) / (sxx + syy + c2);
-            acc += (double)((2.0f * mxy + c1) / (mxx + myy + c1) * cs);
+#pragma unroll
+            for (int q = 0; q < 5; ++q) hb[q][r][c] = m[q];
         }
+        __syncthreads();
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < kSsTH * kSsTW; i += kBlock) {
+            const int r = i / kSsTW, c = i % kSsTW;
+            if (oy + r < Ho && ox + c < Wo) {
+                float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int k = 0; k < kTaps; ++k) {
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) m[q] = fmaf(w[k], hb[q][r + k][c], m[q]);
+                }
+                const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
+                const float mx = m[0] + pvx[ch], my = m[1] + pvy[ch];        // the window means; m[] are about the pivots
+                const float mxx = mx * mx, myy = my * my, mxy = mx * my;
+                const float sxx = m[2] - m[0] * m[0], syy = m[3] - m[1] * m[1], sxy = m[4] - m[0] * m[1];
+                const float cs = (2.0f * sxy + c2) / (sxx + syy + c2);
+                acc += (double)((2.0f * mxy + c1) / (mxx + myy + c1) * cs);
+            }
+        }
+        acc = block_reduce_1(acc, red);
+        if (threadIdx.x == 0) partials[((size_t)(img * 3 + c0 + ch) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = acc;
     }
-    acc = block_reduce_1(acc, red);
-    if (threadIdx.x == 0) partials[((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = acc;
 }
 
 // -------------------------------------------------------------------------------------------------------------------
 // iCID.  grid = (tiles_x, tiles_y, batch); down-sampled size h x w; maps live on the whole h x w grid (reflect padding).
+// SA / SB: the frame sources (ct_frame_src.h); a pixel's three channels come from one at3() per bilinear tap.
 // -------------------------------------------------------------------------------------------------------------------
 constexpr int kIcTW = 32, kIcTH = 16;
 
-// F.interpolate(scale_factor = 1/f, mode = "bilinear", align_corners = False) of one NCHW plane at output pixel (y, x)
-__device__ __forceinline__ float bilinear_down(const float *__restrict__ p, int H, int W, int f, int y, int x) {
-    if (f == 1) return p[(size_t)y * W + x];
+// F.interpolate(scale_factor = 1/f, mode = "bilinear", align_corners = False) of the three channels of a frame at output pixel (y, x)
+template <class S> __device__ __forceinline__ void bilinear_down3(const S &p, int H, int W, int f, int y, int x, float (&v)[3]) {
+    if (f == 1) { p.at3((size_t)y * W + x, v); return; }
     const float sy = fmaxf(((float)y + 0.5f) * (float)f - 0.5f, 0.f), sx = fmaxf(((float)x + 0.5f) * (float)f - 0.5f, 0.f);
     const int y0 = (int)sy, x0 = (int)sx;
     const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
     const float wy = sy - (float)y0, wx = sx - (float)x0;
-    const float v00 = p[(size_t)y0 * W + x0], v01 = p[(size_t)y0 * W + x1], v10 = p[(size_t)y1 * W + x0], v11 = p[(size_t)y1 * W + x1];
-    return (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
+    float v00[3], v01[3], v10[3], v11[3];
+    p.at3((size_t)y0 * W + x0, v00); p.at3((size_t)y0 * W + x1, v01); p.at3((size_t)y1 * W + x0, v10); p.at3((size_t)y1 * W + x1, v11);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (1.f - wy) * ((1.f - wx) * v00[c] + wx * v01[c]) + wy * ((1.f - wx) * v10[c] + wx * v11[c]);
 }
 
-__global__ __launch_bounds__(kBlock) void icid_tile_kernel(const float *__restrict__ a, const float *__restrict__ b, int H, int W, int f, int h,
-                                                           int w_, double *__restrict__ partials) {
+template <class SA, class SB>
+__global__ __launch_bounds__(kBlock) void icid_tile_kernel(const typename SA::elem *__restrict__ a, const typename SB::elem *__restrict__ b, int H, int W,
+                                                           int f, int h, int w_, double *__restrict__ partials) {
     // base planes: L1, C1, L2, C2, sqrt(H) of utils/icid.py:69-111
     __shared__ float base[5][kIcTH + kHalo][kIcTW + kHalo];
     __shared__ float hb[11][kIcTH + kHalo][kIcTW];
     __shared__ float w[kTaps];
+    __shared__ float tab[SA::kTable || SB::kTable ? 256 : 1];
     __shared__ double red[4];
     const int img = blockIdx.z;
-    const float *pa = a + (size_t)img * 3 * H * W, *pb = b + (size_t)img * 3 * H * W;
-    const size_t P = (size_t)H * W;
     const int ox = blockIdx.x * kIcTW, oy = blockIdx.y * kIcTH;
     gauss_weights(w, 2.0f);
+    if constexpr (SA::kTable || SB::kTable) {
+        fill_u8_table_f32(tab);
+        __syncthreads();
+    }
+    const SA pa(a, img, H, W, tab);
+    const SB pb(b, img, H, W, tab);
     for (int i = threadIdx.x; i < (kIcTH + kHalo) * (kIcTW + kHalo); i += kBlock) {
         const int r = i / (kIcTW + kHalo), c = i % (kIcTW + kHalo);
         const int y = reflect(oy + r - 5, h), x = reflect(ox + c - 5, w_);
         float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         if (y >= 0 && y < h && x >= 0 && x < w_) {       // tiles past the image edge: unused entries
-            float L1, A1, B1, L2, A2, B2;
-            rgb_to_lab_f32(bilinear_down(pa, H, W, f, y, x), bilinear_down(pa + P, H, W, f, y, x), bilinear_down(pa + 2 * P, H, W, f, y, x), L1, A1, B1);
-            rgb_to_lab_f32(bilinear_down(pb, H, W, f, y, x), bilinear_down(pb + P, H, W, f, y, x), bilinear_down(pb + 2 * P, H, W, f, y, x), L2, A2, B2);
+            float L1, A1, B1, L2, A2, B2, ra[3], rb[3];
+            bilinear_down3(pa, H, W, f, y, x, ra);
+            bilinear_down3(pb, H, W, f, y, x, rb);
+            rgb_to_lab_f32(ra[0], ra[1], ra[2], L1, A1, B1);
+            rgb_to_lab_f32(rb[0], rb[1], rb[2], L2, A2, B2);
             const float C1 = sqrtf(A1 * A1 + B1 * B1), C2 = sqrtf(A2 * A2 + B2 * B2);
             const float dA = A1 - A2, dB = B1 - B2, dC = C1 - C2;
             const float Hd = dA * dA + dB * dB - dC * dC;
@@ -280,49 +333,83 @@ int launch_psnr_finish(const double *partials, int n_blocks, int stride, int64_t
     return CT_OK;
 }
 
+static size_t metric_workspace_bytes(int height, int width, int batch) {
+    if (height < 1 || width < 1 || batch < 0) return 0;
+    const int f = metric_factor(height, width);
+    const size_t t_ssim = (size_t)((width / f + kSsTW - 1) / kSsTW) * ((height / f + kSsTH - 1) / kSsTH) * 3;
+    const size_t t_icid = (size_t)((width / f + kIcTW - 1) / kIcTW) * ((height / f + kIcTH - 1) / kIcTH);
+    return (t_ssim > t_icid ? t_ssim : t_icid) * (size_t)batch * sizeof(double) + 64;
+}
+
+// the SSIM / iCID entries of one pair of frame sources: checks, the tile launch, the finishing launch
+template <class SA, class SB>
+static int frame_ssim(const typename SA::elem *a, const typename SB::elem *b, int height, int width, int batch, double *out, void *ws, size_t ws_bytes,
+                      void *stream) {
+    if (!a || !b || !out || height < 1 || width < 1 || batch < 0) return CT_E_BADARG;
+    if (batch == 0) return CT_OK;
+    const int f = metric_factor(height, width);
+    const int Hp = height / f, Wp = width / f;
+    if (Hp < kTaps || Wp < kTaps) return CT_E_BADARG;                          // piq asserts the kernel fits the image
+    if (!ws || ws_bytes < metric_workspace_bytes(height, width, batch)) return CT_E_WORKSPACE;
+    const int Ho = Hp - kHalo, Wo = Wp - kHalo;
+    const int tx = (Wo + kSsTW - 1) / kSsTW, ty = (Ho + kSsTH - 1) / kSsTH;
+    constexpr size_t lds = ssim_lds_bytes(SA::kHwc ? 3 : 1);
+    auto kern = ssim_tile_kernel<SA, SB>;
+    static DynLdsAttr attr;             // per instantiation, per device (the HWC form takes 69 KB)
+    {
+        const hipError_t e = attr.ensure(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(tx, ty, SA::kHwc ? batch : batch * 3), dim3(kBlock), lds, (hipStream_t)stream, a, b, height, width, f, Hp, Wp,
+                       (double *)ws);
+    CT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(metric_finish_kernel, dim3(batch), dim3(kBlock), 0, (hipStream_t)stream, (const double *)ws, tx * ty * 3, (double)Ho * Wo * 3.0,
+                       1.0, 0.0, out);
+    CT_CHECK_LAUNCH();
+    return CT_OK;
+}
+
+template <class SA, class SB>
+static int frame_icid(const typename SA::elem *a, const typename SB::elem *b, int height, int width, int batch, double *out, void *ws, size_t ws_bytes,
+                      void *stream) {
+    if (!a || !b || !out || height < 1 || width < 1 || batch < 0) return CT_E_BADARG;
+    if (batch == 0) return CT_OK;
+    const int f = metric_factor(height, width);
+    const int h = (int)__builtin_floor((double)height * (1.0 / f)), w = (int)__builtin_floor((double)width * (1.0 / f));
+    if (h < 6 || w < 6) return CT_E_BADARG;                                    // reflect padding of 5 needs more than 5 pixels
+    if (!ws || ws_bytes < metric_workspace_bytes(height, width, batch)) return CT_E_WORKSPACE;
+    const dim3 grid((w + kIcTW - 1) / kIcTW, (h + kIcTH - 1) / kIcTH, batch);
+    hipLaunchKernelGGL((icid_tile_kernel<SA, SB>), grid, dim3(kBlock), 0, (hipStream_t)stream, a, b, height, width, f, h, w, (double *)ws);
+    CT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(metric_finish_kernel, dim3(batch), dim3(kBlock), 0, (hipStream_t)stream, (const double *)ws, (int)(grid.x * grid.y), (double)h * w,
+                       -1.0, 1.0, out);
+    CT_CHECK_LAUNCH();
+    return CT_OK;
+}
+
 }  // namespace ct
 
 extern "C" {
 
-size_t ct_metric_workspace_bytes(int height, int width, int batch) {
-    if (height < 1 || width < 1 || batch < 0) return 0;
-    const int f = ct::metric_factor(height, width);
-    const size_t t_ssim = (size_t)((width / f + ct::kSsTW - 1) / ct::kSsTW) * ((height / f + ct::kSsTH - 1) / ct::kSsTH) * 3;
-    const size_t t_icid = (size_t)((width / f + ct::kIcTW - 1) / ct::kIcTW) * ((height / f + ct::kIcTH - 1) / ct::kIcTH);
-    return (t_ssim > t_icid ? t_ssim : t_icid) * (size_t)batch * sizeof(double) + 64;
-}
+size_t ct_metric_workspace_bytes(int height, int width, int batch) { return ct::metric_workspace_bytes(height, width, batch); }
 
 int ct_frame_ssim_f32(const float *a, const float *b, int height, int width, int batch, double *out, void *ws, size_t ws_bytes, void *stream) {
-    if (!a || !b || !out || height < 1 || width < 1 || batch < 0) return CT_E_BADARG;
-    if (batch == 0) return CT_OK;
-    const int f = ct::metric_factor(height, width);
-    const int Hp = height / f, Wp = width / f;
-    if (Hp < ct::kTaps || Wp < ct::kTaps) return CT_E_BADARG;                 // piq asserts the kernel fits the image
-    if (!ws || ws_bytes < ct_metric_workspace_bytes(height, width, batch)) return CT_E_WORKSPACE;
-    const int Ho = Hp - ct::kHalo, Wo = Wp - ct::kHalo;
-    const dim3 grid((Wo + ct::kSsTW - 1) / ct::kSsTW, (Ho + ct::kSsTH - 1) / ct::kSsTH, batch * 3);
-    hipLaunchKernelGGL(ct::ssim_tile_kernel, grid, dim3(ct::kBlock), 0, (hipStream_t)stream, a, b, height, width, f, Hp, Wp, (double *)ws);
-    CT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ct::metric_finish_kernel, dim3(batch), dim3(ct::kBlock), 0, (hipStream_t)stream, (const double *)ws,
-                       (int)(grid.x * grid.y * 3), (double)Ho * Wo * 3.0, 1.0, 0.0, out);
-    CT_CHECK_LAUNCH();
-    return CT_OK;
+    return ct::frame_ssim<ct::PlanarF32, ct::PlanarF32>(a, b, height, width, batch, out, ws, ws_bytes, stream);
 }
 
 int ct_frame_icid_f32(const float *a, const float *b, int height, int width, int batch, double *out, void *ws, size_t ws_bytes, void *stream) {
-    if (!a || !b || !out || height < 1 || width < 1 || batch < 0) return CT_E_BADARG;
-    if (batch == 0) return CT_OK;
-    const int f = ct::metric_factor(height, width);
-    const int h = (int)__builtin_floor((double)height * (1.0 / f)), w = (int)__builtin_floor((double)width * (1.0 / f));
-    if (h < 6 || w < 6) return CT_E_BADARG;                                    // reflect padding of 5 needs more than 5 pixels
-    if (!ws || ws_bytes < ct_metric_workspace_bytes(height, width, batch)) return CT_E_WORKSPACE;
-    const dim3 grid((w + ct::kIcTW - 1) / ct::kIcTW, (h + ct::kIcTH - 1) / ct::kIcTH, batch);
-    hipLaunchKernelGGL(ct::icid_tile_kernel, grid, dim3(ct::kBlock), 0, (hipStream_t)stream, a, b, height, width, f, h, w, (double *)ws);
-    CT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ct::metric_finish_kernel, dim3(batch), dim3(ct::kBlock), 0, (hipStream_t)stream, (const double *)ws,
-                       (int)(grid.x * grid.y), (double)h * w, -1.0, 1.0, out);
-    CT_CHECK_LAUNCH();
-    return CT_OK;
+    return ct::frame_icid<ct::PlanarF32, ct::PlanarF32>(a, b, height, width, batch, out, ws, ws_bytes, stream);
+}
+
+// the same metrics read from a frame group's own buffers: the result as float32 HWC (clamped as it is read), the ground truth as bytes
+int ct_frame_ssim_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int height, int width, int batch, double *out, void *ws, size_t ws_bytes,
+                         void *stream) {
+    return ct::frame_ssim<ct::ResultHwcF32, ct::GtHwcU8>(result_hwc, gt_hwc, height, width, batch, out, ws, ws_bytes, stream);
+}
+
+int ct_frame_icid_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int height, int width, int batch, double *out, void *ws, size_t ws_bytes,
+                         void *stream) {
+    return ct::frame_icid<ct::ResultHwcF32, ct::GtHwcU8>(result_hwc, gt_hwc, height, width, batch, out, ws, ws_bytes, stream);
 }
 
 int ct_frame_psnr_f32(const float *a, const float *b, int64_t n_elems, int batch, double *out, void *ws, size_t ws_bytes, void *stream) {

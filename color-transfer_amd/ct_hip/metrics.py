@@ -20,6 +20,9 @@ SIGNATURES.update({
     "ct_fsim_stage_offsets": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_sz)]),
     "ct_fsim_setup_f32": (_c_int, [_c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
     "ct_frame_fsim_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_frame_ssim_hwc_u8": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_frame_icid_hwc_u8": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_frame_fsim_hwc_u8": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
 })
 
 
@@ -125,13 +128,9 @@ def _fsim_ws(device, batch, h, w):
     return ws[off:off + need]
 
 
-def frame_fsim(a, b):
-    """Per-frame piq.fsim(a, b) (chromatic, piq defaults, data range 1) of float32 [B,3,H,W] batches -> float64 [B]
-    (methods/__init__.py:34).  The filter bank of a frame size is built on the device at first use and cached."""
-    _require_cuda(a, b)
-    if a.shape != b.shape or a.dim() != 4 or a.shape[1] != 3 or a.dtype != torch.float32 or b.dtype != torch.float32:
-        raise CtHipError("ct_frame_fsim_f32 needs two float32 [B,3,H,W] tensors of one shape")
-    B, _, h, w = a.shape
+def _frame_fsim(name, a, b, B, h, w):
+    """the FSIM entry `name` on B frames of h x w; the filter bank of a frame size is built on the device at first use and cached,
+    one cache for the planar and the HWC entry"""
     out = torch.empty((B,), dtype=torch.float64, device=a.device)
     if B == 0:
         return out
@@ -148,8 +147,62 @@ def frame_fsim(a, b):
         tab = (filters, consts)
         with _lock:
             _fsim_tables[key] = tab
-    check(lib().ct_frame_fsim_f32(_ptr(a), _ptr(b), _ptr(out), B, h, w, _ptr(tab[0]), _ptr(tab[1]), _ptr(ws), ws.numel(), _stream()))
+    check(getattr(lib(), name)(_ptr(a), _ptr(b), _ptr(out), B, h, w, _ptr(tab[0]), _ptr(tab[1]), _ptr(ws), ws.numel(), _stream()))
     return out
+
+
+def frame_fsim(a, b):
+    """Per-frame piq.fsim(a, b) (chromatic, piq defaults, data range 1) of float32 [B,3,H,W] batches -> float64 [B]
+    (methods/__init__.py:34).  The filter bank of a frame size is built on the device at first use and cached."""
+    _require_cuda(a, b)
+    if a.shape != b.shape or a.dim() != 4 or a.shape[1] != 3 or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise CtHipError("ct_frame_fsim_f32 needs two float32 [B,3,H,W] tensors of one shape")
+    return _frame_fsim("ct_frame_fsim_f32", a, b, a.shape[0], a.shape[2], a.shape[3])
+
+
+def _check_hwc(name, result, gt_u8):
+    """a frame group's own buffers: float32 [B,H,W,3] (unclamped result) and uint8 [B,H,W,3] (ground truth), one device, contiguous;
+    a view with a storage offset (a slice of a larger group) is fine -> (B, H, W)"""
+    if not (torch.is_tensor(result) and torch.is_tensor(gt_u8)):
+        raise CtHipError("%s needs two tensors" % name)
+    if (result.dtype != torch.float32 or gt_u8.dtype != torch.uint8 or result.dim() != 4 or result.shape[3] != 3
+            or result.shape != gt_u8.shape):
+        raise CtHipError("%s needs a float32 [B,H,W,3] result and a uint8 [B,H,W,3] ground truth of one shape (got %s %s and %s %s)"
+                         % (name, result.dtype, tuple(result.shape), gt_u8.dtype, tuple(gt_u8.shape)))
+    if not (result.is_contiguous() and gt_u8.is_contiguous()):
+        raise CtHipError("%s needs contiguous tensors" % name)
+    if not (result.is_cuda and gt_u8.is_cuda) or result.device != gt_u8.device:
+        raise CtHipError("%s needs both tensors on one GPU" % name)
+    _check_device(result)
+    return result.shape[0], result.shape[1], result.shape[2]
+
+
+def _frame_metric_hwc(name, result, gt_u8):
+    B, h, w = _check_hwc(name, result, gt_u8)
+    out = torch.empty((B,), dtype=torch.float64, device=result.device)
+    if B == 0:
+        return out
+    ws = workspace(CT_WS_LAB_STATS, 0, B, result.device, need=lib().ct_metric_workspace_bytes(h, w, B))
+    check(getattr(lib(), name)(_ptr(result), _ptr(gt_u8), h, w, B, _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def frame_ssim_hwc(result, gt_u8):
+    """frame_ssim read from a frame group's own buffers: result float32 [B,H,W,3] (clamped to [0, 1] as it is read, a NaN stays),
+    gt_u8 uint8 [B,H,W,3] (k -> float32(k) / 255) -> float64 [B]; bitwise frame_ssim(result.clamp(0, 1) as NCHW, gt_u8.float() / 255
+    as NCHW), without those passes."""
+    return _frame_metric_hwc("ct_frame_ssim_hwc_u8", result, gt_u8)
+
+
+def frame_icid_hwc(result, gt_u8):
+    """frame_icid read from a frame group's own buffers (see frame_ssim_hwc) -> float64 [B]"""
+    return _frame_metric_hwc("ct_frame_icid_hwc_u8", result, gt_u8)
+
+
+def frame_fsim_hwc(result, gt_u8):
+    """frame_fsim read from a frame group's own buffers (see frame_ssim_hwc) -> float64 [B]; the filter bank cache is frame_fsim's"""
+    B, h, w = _check_hwc("ct_frame_fsim_hwc_u8", result, gt_u8)
+    return _frame_fsim("ct_frame_fsim_hwc_u8", result, gt_u8, B, h, w)
 
 
 def _fsim_stages(a, b):

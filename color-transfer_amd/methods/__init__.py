@@ -4,7 +4,8 @@
 (methods/__init__.py:14-16); `forward(batch)` applies it to every sample of the batch
 (methods/__init__.py:18-27) and `test_step` clamps and scores the result (methods/__init__.py:29-40):
 PSNR, SSIM, FSIM and iCID per frame on the GPU (ct_frame_*_f32; piq / kornia / torchvision arithmetic restated, see
-oracle/metrics.py).
+oracle/metrics.py).  Whole groups of uint8 frames go through `test_group` / `predict_group` instead (`takes_groups()`); with
+`metric_groups=True` for any metric list: `test_group_metrics` scores a group's own buffers (ct_frame_*_hwc_u8).
 
 If the resolved module also offers a device-resident variant `<func>_cuda`, the batch never leaves
 the GPU; otherwise the numpy callable is used through the same host round trip as the reference.
@@ -92,7 +93,7 @@ ACG_SPEC = "methods.iterative.automated_color_grading"
 
 
 class Runner(torch.nn.Module):
-    def __init__(self, func_spec, metrics=None, byte_groups=False, iterative_groups=False, grading_groups=False):
+    def __init__(self, func_spec, metrics=None, byte_groups=False, iterative_groups=False, grading_groups=False, metric_groups=False):
         """func_spec: the reference's only argument (methods/__init__.py:12).  metrics (not in the reference): which of psnr, ssim,
         fsim, icid test_step computes -- default all four, like the reference; `psnr` alone lets the Reinhard transfer take its
         fused uint8 entry (test_group).  byte_groups (not in the reference; `--model.byte_groups true`): with `psnr` alone, MK
@@ -100,8 +101,12 @@ class Runner(torch.nn.Module):
         iterative_groups (not in the reference; `--model.iterative_groups true`): with `psnr` alone, the iterative distribution
         transfer takes whole groups of uint8 frames (ct_hip.idt_u8, one draw of rotations per frame in frame order).
         grading_groups (not in the reference; `--model.grading_groups true`): the same for automated_color_grading (ct_hip.acg_u8:
-        the grouped IDT, then the regrain of the whole group in the launches of one frame)."""
+        the grouped IDT, then the regrain of the whole group in the launches of one frame).
+        metric_groups (not in the reference; `--model.metric_groups true`): whole groups of uint8 frames are taken with ANY metric
+        list, the default four included -- SSIM, FSIM and iCID then read the group's own buffers (test_group_metrics).  Which spec
+        is grouped still depends on the three flags above."""
         super().__init__()
+        self.metric_groups = bool(metric_groups)
         self.byte_groups = bool(byte_groups)
         self.iterative_groups = bool(iterative_groups)
         self.grading_groups = bool(grading_groups)
@@ -118,11 +123,12 @@ class Runner(torch.nn.Module):
         self._out = None
 
     def takes_groups(self):
-        """True when whole groups of uint8 frames go through test_group / predict_group, which needs PSNR as the only metric: the
+        """True when whole groups of uint8 frames go through test_group / predict_group, which needs PSNR as the only metric (or
+        metric_groups: then test_group_metrics scores the group): the
         Reinhard transfer (ONE fused call: ct_reinhard_psnr_u8 reads the bytes; k / 255 and its gamma expansion come from tables
         inside the kernel), with byte_groups MK in its default decomposition (ct_mk_u8) and Xiao (its pieces on bytes), and with
         iterative_groups the iterative distribution transfer (ct_idt_u8), with grading_groups automated_color_grading (ct_acg_u8)."""
-        if self.metrics != ("psnr",):
+        if self.metrics != ("psnr",) and not self.metric_groups:
             return False
         if self.func_spec == IDT_SPEC:
             return self.iterative_groups
@@ -162,6 +168,25 @@ class Runner(torch.nn.Module):
             psnr_out.copy_(ct_hip.frame_psnr(out.clamp(0, 1), group_u8[2].float() / 255))
         else:
             ct_hip.reinhard_persist(group_u8[0], group_u8[1], gt=group_u8[2], out=out, psnr_out=psnr_out)
+        return out
+
+    def test_group_metrics(self, group_u8, table):
+        """group_u8 as for test_group; table: float64 [k, 4] rows of the caller's table in METRICS order (PSNR, SSIM, FSIM, iCID).
+        test_group as it is, into a [k, 2] record; then the requested columns from that record and from ct_hip.frame_ssim_hwc /
+        frame_fsim_hwc / frame_icid_hwc on test_group's float32 result (clamped as it is read) and the ground-truth bytes
+        group_u8[2].  Columns that were not requested become NaN.  No torch kernel between the calls but the column copies, no host
+        synchronisation.  Returns test_group's result."""
+        import ct_hip
+        k = group_u8.shape[1]
+        rec = torch.empty((k, 2), dtype=torch.float64, device=group_u8.device)
+        out = self.test_group(group_u8, rec)
+        gt = group_u8[2]
+        table.fill_(float("nan"))
+        if "psnr" in self.metrics:
+            table[:, 0].copy_(rec[:, 1])
+        for col, name, fn in ((1, "ssim", ct_hip.frame_ssim_hwc), (2, "fsim", ct_hip.frame_fsim_hwc), (3, "icid", ct_hip.frame_icid_hwc)):
+            if name in self.metrics:
+                table[:, col].copy_(fn(out, gt))
         return out
 
     def predict_group(self, group_u8):

@@ -49,6 +49,13 @@ before, file by file.  Under CT_CLI_DEVICE=cpu it is refused before the first fr
 `--model.metrics psnr` on a loader of uint8 groups): MK and Xiao, the iterative distribution transfer, automated colour grading take a
 whole group of uint8 frames per call (`Runner.takes_groups()`, `test_group`, `predict_group`) instead of one float32 frame.  Each flag
 touches its own methods only; without them nothing changes.
+
+`--model.metric_groups true` (test, predict; `Runner` on a loader of uint8 groups): the grouped route is taken with ANY metric list, the
+default four included.  `test` fills its [n, 4] table through `Runner.test_group_metrics`: the grouped transfer + PSNR as above, then
+SSIM, FSIM and iCID read the group's float32 result and the ground-truth bytes where they lie (ct_hip.frame_*_hwc), no clamp, permute
+or conversion pass in between.  Which methods are grouped still depends on the three flags above; with `--model.metrics psnr` the flag
+changes nothing.  `predict` follows `Runner.takes_groups()` and is therefore grouped under the flag for any metric list (it computes no
+metric).  Under CT_CLI_DEVICE=cpu the flag is accepted and the per-frame route runs as before.  Without the flag nothing changes.
 """
 import importlib
 import inspect
@@ -324,12 +331,17 @@ def _test(ctx, timing):
         if grouped:
             # uint8 frames in pinned groups (configs[4]): one upload and ONE fused call per group -- transfer + clamp + PSNR of
             # Runner.test_step (methods/__init__.py:29-32) -- no torch kernel in the loop, one gather at the end
-            rec = torch.zeros((max(len(mine), 1), 2), dtype=torch.float64, device=device)
+            # --model.metric_groups: the [n, 4] table itself, filled by test_group_metrics (SSIM, FSIM, iCID from the group's buffers)
+            # (with PSNR alone the flag changes nothing: the route above)
+            whole = bool(getattr(model, "metric_groups", False)) and tuple(getattr(model, "metrics", ())) != ("psnr",)
+            rec = (torch.full((len(mine), len(METRICS)), float("nan"), dtype=torch.float64, device=device) if whole else
+                   torch.zeros((max(len(mine), 1), 2), dtype=torch.float64, device=device))
+            score = model.test_group_metrics if whole else model.test_group
 
             def run(indices):
                 n = 0
                 for ids, dev in prefetch_groups(frames, indices, device):
-                    model.test_group(dev, rec[n:n + len(ids)])
+                    score(dev, rec[n:n + len(ids)])
                     n += len(ids)
 
             if timing is not None and li == 0:
@@ -340,8 +352,11 @@ def _test(ctx, timing):
                 import time
                 t0 = time.perf_counter()
             run(mine)
-            local = torch.full((len(mine), len(METRICS)), float("nan"), dtype=torch.float64, device=device)
-            local[:, 0] = rec[:len(mine), 1]
+            if whole:
+                local = rec
+            else:
+                local = torch.full((len(mine), len(METRICS)), float("nan"), dtype=torch.float64, device=device)
+                local[:, 0] = rec[:len(mine), 1]
         else:
             if timing is not None and li == 0:
                 fence()

@@ -331,6 +331,24 @@ int ct_frame_ssim_f32(const float *a, const float *b, int height, int width, int
 int ct_frame_icid_f32(const float *a, const float *b, int height, int width, int batch, double *out, void *ws,
                       size_t ws_bytes, void *stream);
 
+/* ---- SSIM, iCID and FSIM read from a frame group's own buffers (csrc/ct_frame_src.h).  Entries added under ABI 9 (no argument
+ * list changed).  result_hwc: float32 [batch][height][width][3], what a grouped transfer writes: NOT clamped -- every value is
+ * clamped to [0, 1] as it is read, and a NaN stays a NaN (a frame of NaNs, as a persistent launch that gave up leaves it, scores
+ * NaN).  gt_hwc: uint8 [batch][height][width][3]; byte k stands for (float)k / 255.0f (IEEE division, from a 256-entry table in
+ * LDS).  Any byte alignment of gt_hwc; result_hwc on 4 bytes.
+ * Contract: ct_frame_X_hwc_u8(a, b) is bitwise ct_frame_X_f32(clamp(a, 0, 1) as NCHW, float32(b) / 255 as NCHW) -- the same
+ * kernels instantiated on another frame source, the same statements in the same order, the same partial sums in the same slots.
+ * Workspaces are the planar entries' (ct_metric_workspace_bytes, ct_fsim_workspace_bytes; 256-byte aligned for FSIM), the filter
+ * bank and constants those of ct_fsim_setup_f32, and the return codes follow the planar entries case by case: CT_E_BADARG for a
+ * null pointer, batch < 0 and a frame too small for the metric, CT_E_WORKSPACE for a missing or short workspace, CT_OK and
+ * nothing launched for batch == 0.  15 bytes read per pixel and metric.                                                        */
+int ct_frame_ssim_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int height, int width, int batch, double *out,
+                         void *ws, size_t ws_bytes, void *stream);
+int ct_frame_icid_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int height, int width, int batch, double *out,
+                         void *ws, size_t ws_bytes, void *stream);
+int ct_frame_fsim_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, double *out, int batch, int h, int w,
+                         const float *filters, const double *consts, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- a4: methods.iterative.iterative_distribution_transfer (methods/iterative.py:8-59) ----
  * Per iteration: projection on the rotated axes (float64, fma chain), exact lo/hi, 2x3 histograms
  * with numpy's bin rule (LDS-binned integer atomics), cumulative LUT, np.interp apply with the
