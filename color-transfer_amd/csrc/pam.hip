@@ -257,7 +257,7 @@ static int launch_pam(const PamArgs &a, int N, hipStream_t s) {
     static_assert(96 * (kPamJC + 1) <= kPamC * kPamKC, "V chunk must fit the K chunk region");
     if (a.C != kPamC) return CT_E_BADARG;
     const int tq = pam_tq(a.W);
-    if (tq == 0) return CT_E_BADARG;   // W > 1982: needs the streaming (online-softmax) variant
+    if (tq == 0) return CT_E_BADARG;   // W > 1983 (32 queries up to W = 959, 16 up to 1983): needs the streaming (online-softmax) variant
     const size_t lds = ((size_t)tq * (a.W | 1) + kPamC * tq + kPamC * kPamKC) * sizeof(float);
     return tq == 32 ? launch_pam_tq<MODE, 32>(a, N, s, lds) : launch_pam_tq<MODE, 16>(a, N, s, lds);
 }

@@ -588,7 +588,7 @@ int ct_attention_tokens_f32(const float *q, const float *k, const float *v, cons
                             float *out, int batch, int len, int cv, float scale, int nsplit, float *ws,
                             size_t ws_bytes, long long kv_shift, void *stream);
 /* Streaming parallax attention on 64-channel row tokens (pasmnet/attention.py:39-46, utils.py:30-35,123-125), for
- * image widths whose score tile does not fit LDS (ct_pam_* need w <= 1982) and as the faster path in general:
+ * image widths whose score tile does not fit LDS (ct_pam_* need w <= 1983) and as the faster path in general:
  *   ct_attention_rows64_f32 : out[b][i][0:96] = softmax_j(q_i.k_j*scale) v[b][j][0:96]   (v != NULL), and/or the row
  *                             statistics stats[b][i] = (max, sum) of that softmax (v == NULL: statistics only)
  *   ct_attention_colsum64_f32: colsum[b][j] = sum_i exp(q_i.k_j*scale - max_i) / sum_i  (the valid-mask numerator),

@@ -156,7 +156,8 @@ def test_forward_full_size_split_vs_exact_convs():
 
 @pytest.mark.parametrize("h,w", [(3, 70), (2, 512), (2, 1030), (2, 1920)])
 def test_pam_kernels_vs_torch_reference(h, w):
-    """ct_pam_attend_f32 / ct_pam_valid_f32 alone, including the 16-query variant used for W > 992 (1080p)
+    """ct_pam_attend_f32 / ct_pam_valid_f32 alone, including the 16-query variant used for W > 959 (1080p; derived in
+    tests/test_pam_edges_host.py)
     and a width that is no multiple of 4 (scalar staging path)."""
     import ct_hip
     gen = torch.Generator().manual_seed(w)

@@ -36,6 +36,7 @@ RES = "tests/test_resize_gpu.py::"
 IDT = "tests/test_idt_gpu.py::"
 RG = "tests/test_regrain.py::"
 RP = "tests/test_reinhard_persist_gpu.py::"
+EDGE = "tests/test_pam_edges_gpu.py::"
 ME = "tests/test_kernel_variants_gpu.py::"
 
 # test_gconv's geometries that csrc/conv_direct.hip takes: cout <= 4 (cfg10, cfg17 - cfg19) and the 7x7 kernels on <= 3 channels
@@ -58,7 +59,12 @@ GROUPS = {
         + [GM + "test_small_cout_conv_zero_padding_is_a_select[cfg%d]" % c for c in range(3)]
         + ["tests/test_disparity_gpu.py::test_pam_streaming_disp_ini[4-512]", "tests/test_dcmcs3di_gpu.py::test_pam_streaming_vs_torch_reference[3-70]"]
         + [WS + "test_conv_ws_vs_float64[cfg%d-False]" % c for c in range(6)]
-        + [WS + "test_conv_ws_writes_only_its_output[cfg%d]" % c for c in range(3)]),
+        + [WS + "test_conv_ws_writes_only_its_output[cfg%d]" % c for c in range(3)]
+        # the streaming family on peaked inputs (tests/pam_edges_common.py), same bounds: lengths at the tile / workgroup edges, every
+        # grid of the workgroup-order test, NaN locality
+        + [EDGE + "test_streaming_lengths[%s-%d]" % (c, l) for c in ("flat", "mid", "peaked", "twin", "ramp-up", "ramp-down") for l in (33, 128, 129)]
+        + [EDGE + "test_streaming_grid_order[%d-%d]" % g for g in ((129, 4), (33, 9), (33, 17), (385, 6), (257, 11))]
+        + [EDGE + "test_streaming_nan_stays_where_the_reference_puts_it[%s]" % w for w in ("query", "key", "value")]),
     # every launch-geometry cap at its floor: grid-stride loops take several trips on 17x31 .. 273x481 frames, seven persistent
     # workgroups hold more tiles than fit their LDS (300x301: 51 slots), conv_ws cuts its 5..50-row images into 3-row segments
     "small-grids": (
