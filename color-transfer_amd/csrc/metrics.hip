@@ -2,7 +2,8 @@
 //   SSIM  = piq.ssim(result, gt) with piq's defaults (11x11 Gaussian, sigma 1.5, k1 0.01, k2 0.03, data_range 1,
 //           average-pool downsampling by max(1, round(min(H, W) / 256)), "valid" windows, mean over channels and positions)
 //   iCID  = utils/icid.py:28-152 (perceptual intent, all seven maps, bilinear downsampling by the same factor, kornia's
-//           rgb_to_lab, torchvision's 11x11 sigma-2 gaussian_blur with reflect padding)
+//           rgb_to_lab, torchvision's 11x11 sigma-2 gaussian_blur with reflect padding); ct_frame_icid_opt_*: its other two
+//           intents, omit_maps67 and downsampling = False (the maps at the frame's own size) as well
 // piq, kornia and torchvision are third-party and absent offline: their arithmetic is restated from their published
 // sources (oracle/metrics.py says where) -- "parity unpinned" for those calls; SSIM's core is anchored on scikit-image's
 // structural_similarity, iCID's own lines on a run of the reference's utils/icid.py (tests/golden/make_golden_*).
@@ -171,12 +172,21 @@ template <class S> __device__ __forceinline__ void bilinear_down3(const S &p, in
     for (int c = 0; c < 3; ++c) v[c] = (1.f - wy) * ((1.f - wx) * v00[c] + wx * v01[c]) + wy * ((1.f - wx) * v10[c] + wx * v11[c]);
 }
 
-template <class SA, class SB>
+// INTENT (CT_ICID_*): the weights of utils/icid.py:42-47 -- float32 constants, as torch.tensor([...]) makes them; the hue-preserving
+// intent raises the weight of map 5 (hue difference) to 0.02, the chromatic intent that of map 4 (chroma difference) as well.
+// OMIT (omit_maps67): maps 6 and 7 get exponent 0 and torch.pow(x, 0) is 1 for any x, NaN included, so they are exactly dropped: the
+// blurred C1^2, C2^2 and C1 C2 that only they read are not taken (8 of the 11 moment planes remain).  <CT_ICID_PERCEPTUAL, false> is
+// what ct_frame_icid_f32 / ct_frame_icid_hwc_u8 have always launched.
+template <class SA, class SB, int INTENT, bool OMIT>
 __global__ __launch_bounds__(kBlock) void icid_tile_kernel(const typename SA::elem *__restrict__ a, const typename SB::elem *__restrict__ b, int H, int W,
                                                            int f, int h, int w_, double *__restrict__ partials) {
+    constexpr int NP = OMIT ? 8 : 11;                   // moment planes: muL1 muC1 muL2 muC2 L1^2 L2^2 [C1^2 C2^2] sqrt(H) L1L2 [C1C2]
+    constexpr int iH = OMIT ? 6 : 8, iL12 = OMIT ? 7 : 9;
+    constexpr float wC = INTENT == CT_ICID_CHROMATIC ? 0.02f : 0.002f;          // weights[3], chroma difference
+    constexpr float wH = INTENT == CT_ICID_PERCEPTUAL ? 0.002f : 0.02f;         // weights[4], hue difference
     // base planes: L1, C1, L2, C2, sqrt(H) of utils/icid.py:69-111
     __shared__ float base[5][kIcTH + kHalo][kIcTW + kHalo];
-    __shared__ float hb[11][kIcTH + kHalo][kIcTW];
+    __shared__ float hb[NP][kIcTH + kHalo][kIcTW];
     __shared__ float w[kTaps];
     __shared__ float tab[SA::kTable || SB::kTable ? 256 : 1];
     __shared__ double red[4];
@@ -214,49 +224,57 @@ __global__ __launch_bounds__(kBlock) void icid_tile_kernel(const typename SA::el
     const float p0 = base[0][pr][pc], p1 = base[1][pr][pc], p2 = base[2][pr][pc], p3 = base[3][pr][pc];
     for (int i = threadIdx.x; i < (kIcTH + kHalo) * kIcTW; i += kBlock) {
         const int r = i / kIcTW, c = i % kIcTW;
-        float m[11];
+        float m[NP];
 #pragma unroll
-        for (int q = 0; q < 11; ++q) m[q] = 0.f;
+        for (int q = 0; q < NP; ++q) m[q] = 0.f;
 #pragma unroll
         for (int k = 0; k < kTaps; ++k) {
             const float g = w[k], L1 = base[0][r][c + k] - p0, C1 = base[1][r][c + k] - p1, L2 = base[2][r][c + k] - p2,
                         C2 = base[3][r][c + k] - p3;
             m[0] = fmaf(g, L1, m[0]); m[1] = fmaf(g, C1, m[1]); m[2] = fmaf(g, L2, m[2]); m[3] = fmaf(g, C2, m[3]);
-            m[4] = fmaf(g, L1 * L1, m[4]); m[5] = fmaf(g, L2 * L2, m[5]); m[6] = fmaf(g, C1 * C1, m[6]); m[7] = fmaf(g, C2 * C2, m[7]);
-            m[8] = fmaf(g, base[4][r][c + k], m[8]); m[9] = fmaf(g, L1 * L2, m[9]); m[10] = fmaf(g, C1 * C2, m[10]);
+            m[4] = fmaf(g, L1 * L1, m[4]); m[5] = fmaf(g, L2 * L2, m[5]);
+            if constexpr (!OMIT) { m[6] = fmaf(g, C1 * C1, m[6]); m[7] = fmaf(g, C2 * C2, m[7]); }
+            m[iH] = fmaf(g, base[4][r][c + k], m[iH]); m[iL12] = fmaf(g, L1 * L2, m[iL12]);
+            if constexpr (!OMIT) m[10] = fmaf(g, C1 * C2, m[10]);
         }
 #pragma unroll
-        for (int q = 0; q < 11; ++q) hb[q][r][c] = m[q];
+        for (int q = 0; q < NP; ++q) hb[q][r][c] = m[q];
     }
     __syncthreads();
     double acc = 0.0;
     for (int i = threadIdx.x; i < kIcTH * kIcTW; i += kBlock) {
         const int r = i / kIcTW, c = i % kIcTW;
         if (oy + r < h && ox + c < w_) {
-            float m[11];
+            float m[NP];
 #pragma unroll
-            for (int q = 0; q < 11; ++q) m[q] = 0.f;
+            for (int q = 0; q < NP; ++q) m[q] = 0.f;
 #pragma unroll
             for (int k = 0; k < kTaps; ++k) {
 #pragma unroll
-                for (int q = 0; q < 11; ++q) m[q] = fmaf(w[k], hb[q][r + k][c], m[q]);
+                for (int q = 0; q < NP; ++q) m[q] = fmaf(w[k], hb[q][r + k][c], m[q]);
             }
-            const float muL1 = m[0], muC1 = m[1], muL2 = m[2], muC2 = m[3];      // about the pivots, like m[4..7], m[9], m[10]
+            const float muL1 = m[0], muC1 = m[1], muL2 = m[2], muC2 = m[3];      // about the pivots, like the second moments
             const float sL1q = fmaxf(m[4] - muL1 * muL1, 0.f), sL2q = fmaxf(m[5] - muL2 * muL2, 0.f);
-            const float sC1q = fmaxf(m[6] - muC1 * muC1, 0.f), sC2q = fmaxf(m[7] - muC2 * muC2, 0.f);
-            const float sL1 = sqrtf(sL1q), sL2 = sqrtf(sL2q), sC1 = sqrtf(sC1q), sC2 = sqrtf(sC2q);
+            const float sL1 = sqrtf(sL1q), sL2 = sqrtf(sL2q);
             const float dL = (muL1 - muL2) + (p0 - p2), dC = (muC1 - muC2) + (p1 - p3);
-            const float dLq = dL * dL, dCq = dC * dC, dHq = m[8] * m[8];
-            const float sL12 = m[9] - muL1 * muL2, sC12 = m[10] - muC1 * muC2;
-            // perceptual intent: weights (0.002, 10, 10, 0.002, 0.002, 10, 10), exponents (1, 1, 3, 1, 1, 1, 1)
+            const float dLq = dL * dL, dCq = dC * dC, dHq = m[iH] * m[iH];
+            const float sL12 = m[iL12] - muL1 * muL2;
+            // weights (0.002, 10, 10, wC, wH, 10, 10) -- 0.002 and 0.002 for the perceptual intent --, exponents (1, 1, 3, 1, 1, 1, 1)
             const float m1 = 1.f / (0.002f * dLq + 1.f);
             const float m2 = (10.f + 2.f * sL1 * sL2) / (10.f + sL1q + sL2q);
             const float m3 = (10.f + fabsf(sL12)) / (10.f + sL1 * sL2);
-            const float m4 = 1.f / (0.002f * dCq + 1.f);
-            const float m5 = 1.f / (0.002f * dHq + 1.f);
-            const float m6 = (10.f + 2.f * sC1 * sC2) / (10.f + sC1 * sC1 + sC2 * sC2);
-            const float m7 = (10.f + fabsf(sC12)) / (10.f + sC1 * sC2);
-            acc += (double)(m1 * m2 * (m3 * m3 * m3) * m4 * m5 * m6 * m7);
+            const float m4 = 1.f / (wC * dCq + 1.f);
+            const float m5 = 1.f / (wH * dHq + 1.f);
+            if constexpr (OMIT) {
+                acc += (double)(m1 * m2 * (m3 * m3 * m3) * m4 * m5);
+            } else {
+                const float sC1q = fmaxf(m[6] - muC1 * muC1, 0.f), sC2q = fmaxf(m[7] - muC2 * muC2, 0.f);
+                const float sC1 = sqrtf(sC1q), sC2 = sqrtf(sC2q);
+                const float sC12 = m[10] - muC1 * muC2;
+                const float m6 = (10.f + 2.f * sC1 * sC2) / (10.f + sC1 * sC1 + sC2 * sC2);
+                const float m7 = (10.f + fabsf(sC12)) / (10.f + sC1 * sC2);
+                acc += (double)(m1 * m2 * (m3 * m3 * m3) * m4 * m5 * m6 * m7);
+            }
         }
     }
     acc = block_reduce_1(acc, red);
@@ -369,17 +387,41 @@ static int frame_ssim(const typename SA::elem *a, const typename SB::elem *b, in
     return CT_OK;
 }
 
+// iCID's map grid: the frame itself (downsampling off, or f == 1), else what F.interpolate(scale_factor = 1 / f) makes of it
+static void icid_grid(int height, int width, int downsampling, int *f, int *h, int *w) {
+    *f = downsampling ? metric_factor(height, width) : 1;
+    *h = (int)__builtin_floor((double)height * (1.0 / *f));
+    *w = (int)__builtin_floor((double)width * (1.0 / *f));
+}
+
+// one partial per tile of the map grid that `downsampling` selects; with it on, never more than metric_workspace_bytes
+static size_t icid_workspace_bytes(int height, int width, int batch, int downsampling) {
+    if (height < 1 || width < 1 || batch < 0) return 0;
+    int f, h, w;
+    icid_grid(height, width, downsampling, &f, &h, &w);
+    return (size_t)((w + kIcTW - 1) / kIcTW) * ((h + kIcTH - 1) / kIcTH) * (size_t)batch * sizeof(double) + 64;
+}
+
+// options: the ct_frame_icid_opt_* entries, which size their workspace by ct_icid_workspace_bytes; the entries without options pass
+// (CT_ICID_PERCEPTUAL, 0, 1) and keep ct_metric_workspace_bytes
 template <class SA, class SB>
-static int frame_icid(const typename SA::elem *a, const typename SB::elem *b, int height, int width, int batch, double *out, void *ws, size_t ws_bytes,
-                      void *stream) {
+static int frame_icid(const typename SA::elem *a, const typename SB::elem *b, int height, int width, int batch, int intent, int omit_maps67,
+                      int downsampling, bool options, double *out, void *ws, size_t ws_bytes, void *stream) {
     if (!a || !b || !out || height < 1 || width < 1 || batch < 0) return CT_E_BADARG;
+    if (intent < CT_ICID_PERCEPTUAL || intent > CT_ICID_CHROMATIC) return CT_E_BADARG;
     if (batch == 0) return CT_OK;
-    const int f = metric_factor(height, width);
-    const int h = (int)__builtin_floor((double)height * (1.0 / f)), w = (int)__builtin_floor((double)width * (1.0 / f));
+    int f, h, w;
+    icid_grid(height, width, downsampling, &f, &h, &w);
     if (h < 6 || w < 6) return CT_E_BADARG;                                    // reflect padding of 5 needs more than 5 pixels
-    if (!ws || ws_bytes < metric_workspace_bytes(height, width, batch)) return CT_E_WORKSPACE;
+    const size_t need = options ? icid_workspace_bytes(height, width, batch, downsampling) : metric_workspace_bytes(height, width, batch);
+    if (!ws || ws_bytes < need) return CT_E_WORKSPACE;
+    typedef void (*Kernel)(const typename SA::elem *, const typename SB::elem *, int, int, int, int, int, double *);
+    static const Kernel kernels[3][2] = {
+        {icid_tile_kernel<SA, SB, CT_ICID_PERCEPTUAL, false>, icid_tile_kernel<SA, SB, CT_ICID_PERCEPTUAL, true>},
+        {icid_tile_kernel<SA, SB, CT_ICID_HUE_PRESERVING, false>, icid_tile_kernel<SA, SB, CT_ICID_HUE_PRESERVING, true>},
+        {icid_tile_kernel<SA, SB, CT_ICID_CHROMATIC, false>, icid_tile_kernel<SA, SB, CT_ICID_CHROMATIC, true>}};
     const dim3 grid((w + kIcTW - 1) / kIcTW, (h + kIcTH - 1) / kIcTH, batch);
-    hipLaunchKernelGGL((icid_tile_kernel<SA, SB>), grid, dim3(kBlock), 0, (hipStream_t)stream, a, b, height, width, f, h, w, (double *)ws);
+    hipLaunchKernelGGL(kernels[intent][omit_maps67 ? 1 : 0], grid, dim3(kBlock), 0, (hipStream_t)stream, a, b, height, width, f, h, w, (double *)ws);
     CT_CHECK_LAUNCH();
     hipLaunchKernelGGL(metric_finish_kernel, dim3(batch), dim3(kBlock), 0, (hipStream_t)stream, (const double *)ws, (int)(grid.x * grid.y), (double)h * w,
                        -1.0, 1.0, out);
@@ -398,7 +440,14 @@ int ct_frame_ssim_f32(const float *a, const float *b, int height, int width, int
 }
 
 int ct_frame_icid_f32(const float *a, const float *b, int height, int width, int batch, double *out, void *ws, size_t ws_bytes, void *stream) {
-    return ct::frame_icid<ct::PlanarF32, ct::PlanarF32>(a, b, height, width, batch, out, ws, ws_bytes, stream);
+    return ct::frame_icid<ct::PlanarF32, ct::PlanarF32>(a, b, height, width, batch, CT_ICID_PERCEPTUAL, 0, 1, false, out, ws, ws_bytes, stream);
+}
+
+size_t ct_icid_workspace_bytes(int height, int width, int batch, int downsampling) { return ct::icid_workspace_bytes(height, width, batch, downsampling); }
+
+int ct_frame_icid_opt_f32(const float *a, const float *b, int height, int width, int batch, int intent, int omit_maps67, int downsampling, double *out,
+                          void *ws, size_t ws_bytes, void *stream) {
+    return ct::frame_icid<ct::PlanarF32, ct::PlanarF32>(a, b, height, width, batch, intent, omit_maps67, downsampling, true, out, ws, ws_bytes, stream);
 }
 
 // the same metrics read from a frame group's own buffers: the result as float32 HWC (clamped as it is read), the ground truth as bytes
@@ -409,7 +458,14 @@ int ct_frame_ssim_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int hei
 
 int ct_frame_icid_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int height, int width, int batch, double *out, void *ws, size_t ws_bytes,
                          void *stream) {
-    return ct::frame_icid<ct::ResultHwcF32, ct::GtHwcU8>(result_hwc, gt_hwc, height, width, batch, out, ws, ws_bytes, stream);
+    return ct::frame_icid<ct::ResultHwcF32, ct::GtHwcU8>(result_hwc, gt_hwc, height, width, batch, CT_ICID_PERCEPTUAL, 0, 1, false, out, ws, ws_bytes,
+                                                         stream);
+}
+
+int ct_frame_icid_opt_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int height, int width, int batch, int intent, int omit_maps67,
+                             int downsampling, double *out, void *ws, size_t ws_bytes, void *stream) {
+    return ct::frame_icid<ct::ResultHwcF32, ct::GtHwcU8>(result_hwc, gt_hwc, height, width, batch, intent, omit_maps67, downsampling, true, out, ws,
+                                                         ws_bytes, stream);
 }
 
 int ct_frame_psnr_f32(const float *a, const float *b, int64_t n_elems, int batch, double *out, void *ws, size_t ws_bytes, void *stream) {

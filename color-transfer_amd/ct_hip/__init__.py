@@ -19,7 +19,7 @@ from ._core import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SW
 from .linear import (CT_LAB_EXACT, CT_LAB_TABLE, affine3x3, lab_mode, lab_stats, mk, mk_coef, profile_events, reinhard,
                      reinhard_apply, reinhard_persist, reinhard_persist_supported, reinhard_psnr, reinhard_takes_persist,
                      rgb_meancov, set_lab_mode, upload_records)
-from .metrics import (CT_WS_FSIM, DISTORTIONS, distort_u8, fft2d_, frame_fsim, frame_fsim_hwc, frame_icid, frame_icid_hwc, frame_psnr, frame_ssim,
+from .metrics import (CT_WS_FSIM, DISTORTIONS, ICID_INTENTS, icid_intent, distort_u8, fft2d_, frame_fsim, frame_fsim_hwc, frame_icid, frame_icid_hwc, frame_psnr, frame_ssim,
                       frame_ssim_hwc, regrain,
                       _fsim_stages, _fsim_tables)
 from .idt import IdtDebug, idt, idt_u8

@@ -23,6 +23,9 @@ SIGNATURES.update({
     "ct_frame_ssim_hwc_u8": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_sz, _c_p]),
     "ct_frame_icid_hwc_u8": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_sz, _c_p]),
     "ct_frame_fsim_hwc_u8": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_icid_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "ct_frame_icid_opt_f32": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_sz, _c_p]),
+    "ct_frame_icid_opt_hwc_u8": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_sz, _c_p]),
 })
 
 
@@ -99,9 +102,39 @@ def frame_ssim(a, b):
     return _frame_metric("ct_frame_ssim_f32", a, b)
 
 
-def frame_icid(a, b):
-    """Per-frame utils.icid.icid(a, b) (perceptual intent) of float32 [B,3,H,W] batches -> float64 [B] (methods/__init__.py:35)."""
-    return _frame_metric("ct_frame_icid_f32", a, b)
+ICID_INTENTS = {"perceptual": 0, "hue-preserving": 1, "chromatic": 2}              # CT_ICID_* of include/ct_hip.h
+
+
+def icid_intent(intent):
+    """CT_ICID_* of an intent name; anything else raises the reference's ValueError (utils/icid.py:49).  Touches no device."""
+    if not isinstance(intent, str) or intent not in ICID_INTENTS:
+        raise ValueError("Intent should be either 'perceptual', 'hue-preserving', or 'chromatic'")
+    return ICID_INTENTS[intent]
+
+
+def _frame_icid_opt(name, a, b, B, h, w, intent, omit_maps67, downsampling):
+    """the iCID entry with options `name` on B frames of h x w, with the workspace of its map grid"""
+    out = torch.empty((B,), dtype=torch.float64, device=a.device)
+    if B == 0:
+        return out
+    down = 1 if downsampling else 0
+    ws = workspace(CT_WS_LAB_STATS, 0, B, a.device, need=lib().ct_icid_workspace_bytes(h, w, B, down))
+    check(getattr(lib(), name)(_ptr(a), _ptr(b), h, w, B, intent, 1 if omit_maps67 else 0, down, _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def frame_icid(a, b, intent="perceptual", omit_maps67=False, downsampling=True):
+    """Per-frame utils.icid.icid(a, b, intent, omit_maps67, downsampling) of float32 [B,3,H,W] batches -> float64 [B]
+    (methods/__init__.py:35; the arguments of utils/icid.py:28-34).  The defaults call ct_frame_icid_f32, anything else
+    ct_frame_icid_opt_f32: downsampling=False takes the maps at the frames' own size.  An unknown intent raises the reference's
+    ValueError before any device call."""
+    code = icid_intent(intent)
+    if code == 0 and not omit_maps67 and downsampling:
+        return _frame_metric("ct_frame_icid_f32", a, b)
+    _require_cuda(a, b)
+    if a.shape != b.shape or a.dim() != 4 or a.shape[1] != 3 or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise CtHipError("ct_frame_icid_opt_f32 needs two float32 [B,3,H,W] tensors of one shape")
+    return _frame_icid_opt("ct_frame_icid_opt_f32", a, b, a.shape[0], a.shape[2], a.shape[3], code, omit_maps67, downsampling)
 
 _fsim_tables = {}                                  # (device, h, w) -> (filters [16, hp*wp] float32, consts [4, 3] float64)
 CT_WS_FSIM = -7
@@ -194,9 +227,14 @@ def frame_ssim_hwc(result, gt_u8):
     return _frame_metric_hwc("ct_frame_ssim_hwc_u8", result, gt_u8)
 
 
-def frame_icid_hwc(result, gt_u8):
-    """frame_icid read from a frame group's own buffers (see frame_ssim_hwc) -> float64 [B]"""
-    return _frame_metric_hwc("ct_frame_icid_hwc_u8", result, gt_u8)
+def frame_icid_hwc(result, gt_u8, intent="perceptual", omit_maps67=False, downsampling=True):
+    """frame_icid, with its options, read from a frame group's own buffers (see frame_ssim_hwc) -> float64 [B]; the defaults call
+    ct_frame_icid_hwc_u8, anything else ct_frame_icid_opt_hwc_u8"""
+    code = icid_intent(intent)
+    if code == 0 and not omit_maps67 and downsampling:
+        return _frame_metric_hwc("ct_frame_icid_hwc_u8", result, gt_u8)
+    B, h, w = _check_hwc("ct_frame_icid_opt_hwc_u8", result, gt_u8)
+    return _frame_icid_opt("ct_frame_icid_opt_hwc_u8", result, gt_u8, B, h, w, code, omit_maps67, downsampling)
 
 
 def frame_fsim_hwc(result, gt_u8):

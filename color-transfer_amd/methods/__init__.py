@@ -31,11 +31,14 @@ def ssim(x, y):
     return ct_hip.frame_ssim(x.float().contiguous(), y.float().contiguous())
 
 
-def icid(x, y):
-    """utils.icid.icid(x, y) (perceptual intent), per sample [B] (GPU only: ct_frame_icid_f32).  The reference returns
-    the mean over the batch; test loaders use batch size 1 (utils/data.py:168-179), where the two coincide."""
+def icid(x, y, intent="perceptual", omit_maps67=False, downsampling=True):
+    """utils.icid.icid(x, y, intent, omit_maps67, downsampling), per sample [B] (GPU only: ct_frame_icid_f32, with other than
+    the default arguments ct_frame_icid_opt_f32).  The reference returns the mean over the batch (utils.icid.icid here does
+    too); test loaders use batch size 1 (utils/data.py:168-179), where the two coincide.  An unknown intent raises the
+    reference's ValueError before the tensors are looked at."""
     import ct_hip
-    return ct_hip.frame_icid(x.float().contiguous(), y.float().contiguous())
+    ct_hip.icid_intent(intent)
+    return ct_hip.frame_icid(x.float().contiguous(), y.float().contiguous(), intent=intent, omit_maps67=omit_maps67, downsampling=downsampling)
 
 
 def fsim(x, y):
@@ -93,7 +96,8 @@ ACG_SPEC = "methods.iterative.automated_color_grading"
 
 
 class Runner(torch.nn.Module):
-    def __init__(self, func_spec, metrics=None, byte_groups=False, iterative_groups=False, grading_groups=False, metric_groups=False):
+    def __init__(self, func_spec, metrics=None, byte_groups=False, iterative_groups=False, grading_groups=False, metric_groups=False,
+                 icid_intent="perceptual", icid_omit_maps67=False, icid_downsampling=True):
         """func_spec: the reference's only argument (methods/__init__.py:12).  metrics (not in the reference): which of psnr, ssim,
         fsim, icid test_step computes -- default all four, like the reference; `psnr` alone lets the Reinhard transfer take its
         fused uint8 entry (test_group).  byte_groups (not in the reference; `--model.byte_groups true`): with `psnr` alone, MK
@@ -104,8 +108,16 @@ class Runner(torch.nn.Module):
         the grouped IDT, then the regrain of the whole group in the launches of one frame).
         metric_groups (not in the reference; `--model.metric_groups true`): whole groups of uint8 frames are taken with ANY metric
         list, the default four included -- SSIM, FSIM and iCID then read the group's own buffers (test_group_metrics).  Which spec
-        is grouped still depends on the three flags above."""
+        is grouped still depends on the three flags above.
+        icid_intent, icid_omit_maps67, icid_downsampling (the reference calls utils.icid.icid with its defaults, which these are;
+        `--model.icid_intent chromatic` etc.): the other arguments of utils.icid.icid, for test_step and test_group_metrics.  An
+        unknown intent raises the reference's ValueError here."""
         super().__init__()
+        import ct_hip
+        ct_hip.icid_intent(icid_intent)
+        self.icid_intent = icid_intent
+        self.icid_omit_maps67 = bool(icid_omit_maps67)
+        self.icid_downsampling = bool(icid_downsampling)
         self.metric_groups = bool(metric_groups)
         self.byte_groups = bool(byte_groups)
         self.iterative_groups = bool(iterative_groups)
@@ -141,6 +153,9 @@ class Runner(torch.nn.Module):
         if self._out is None or self._out.shape[1:] != group_u8.shape[2:] or self._out.shape[0] < k or self._out.device != group_u8.device:
             self._out = torch.empty((k,) + tuple(group_u8.shape[2:]), dtype=torch.float32, device=group_u8.device)
         return self._out[:k]
+
+    def _icid_options(self):
+        return {"intent": self.icid_intent, "omit_maps67": self.icid_omit_maps67, "downsampling": self.icid_downsampling}
 
     def _iterative_u8(self):
         """the grouped entry of an iterative method (the two have one signature), else None"""
@@ -184,9 +199,11 @@ class Runner(torch.nn.Module):
         table.fill_(float("nan"))
         if "psnr" in self.metrics:
             table[:, 0].copy_(rec[:, 1])
-        for col, name, fn in ((1, "ssim", ct_hip.frame_ssim_hwc), (2, "fsim", ct_hip.frame_fsim_hwc), (3, "icid", ct_hip.frame_icid_hwc)):
+        for col, name, fn in ((1, "ssim", ct_hip.frame_ssim_hwc), (2, "fsim", ct_hip.frame_fsim_hwc)):
             if name in self.metrics:
                 table[:, col].copy_(fn(out, gt))
+        if "icid" in self.metrics:
+            table[:, 3].copy_(ct_hip.frame_icid_hwc(out, gt, **self._icid_options()))
         return out
 
     def predict_group(self, group_u8):
@@ -240,7 +257,8 @@ class Runner(torch.nn.Module):
         result = self(batch).clamp(0, 1)
         gt = batch["gt"].to(result.device)
         out = {}
-        fns = {"psnr": ("Test PSNR", psnr), "ssim": ("Test SSIM", ssim), "fsim": ("Test FSIM", fsim), "icid": ("Test iCID", icid)}
+        fns = {"psnr": ("Test PSNR", psnr), "ssim": ("Test SSIM", ssim), "fsim": ("Test FSIM", fsim),
+               "icid": ("Test iCID", lambda x, y: icid(x, y, **self._icid_options()))}
         for m in self.metrics:
             if m == "psnr" or result.is_cuda:        # SSIM / FSIM / iCID exist on the GPU only
                 out[fns[m][0]] = fns[m][1](result, gt)

@@ -56,6 +56,13 @@ SSIM, FSIM and iCID read the group's float32 result and the ground-truth bytes w
 or conversion pass in between.  Which methods are grouped still depends on the three flags above; with `--model.metrics psnr` the flag
 changes nothing.  `predict` follows `Runner.takes_groups()` and is therefore grouped under the flag for any metric list (it computes no
 metric).  Under CT_CLI_DEVICE=cpu the flag is accepted and the per-frame route runs as before.  Without the flag nothing changes.
+
+`--model.icid_intent perceptual|hue-preserving|chromatic`, `--model.icid_omit_maps67 true`, `--model.icid_downsampling false` (test;
+`Runner`): the other arguments of the reference's `utils.icid.icid(img1, img2, intent, omit_maps67, downsampling)` for the `Test iCID`
+column, on the per-frame route (`test_step`) and on the grouped one (`test_group_metrics`) alike.  hue-preserving and chromatic weight
+the hue (and chroma) difference ten times more; omit_maps67 drops chroma contrast and chroma structure; `icid_downsampling false`
+scores the frame at its own size instead of after the resize by 1 / max(1, round(min(H, W) / 256)).  An unknown intent is refused when
+the model is built, with the reference's message.  The defaults are the reference's: without the flags nothing changes.
 """
 import importlib
 import inspect

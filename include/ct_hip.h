@@ -349,6 +349,27 @@ int ct_frame_icid_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int hei
 int ct_frame_fsim_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, double *out, int batch, int h, int w,
                          const float *filters, const double *consts, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- iCID with the other arguments of utils/icid.py:28-34.  Entries added under ABI 9 (no argument list changed).
+ *   intent        CT_ICID_*: the weights of utils/icid.py:42-47, float32 constants as torch.tensor([...]) makes them --
+ *                 perceptual (0.002, 10, 10, 0.002, 0.002, 10, 10); hue-preserving: weight 5 (hue difference) = 0.02; chromatic:
+ *                 weights 4 (chroma difference) and 5 = 0.02
+ *   omit_maps67   non-zero: maps 6 (chroma contrast) and 7 (chroma structure) get exponent 0, i.e. are dropped exactly; the
+ *                 three blurred moments only they read are not computed
+ *   downsampling  zero: the maps are taken at the frame's own size (f = 1) instead of after the bilinear resize by 1 / f
+ * The frames, `out` and the two frame sources are those of ct_frame_icid_f32 / ct_frame_icid_hwc_u8, whose kernels these are:
+ * (CT_ICID_PERCEPTUAL, 0, 1) gives their results bit for bit, and the hwc_u8 form is bitwise the f32 form on the converted
+ * tensors under every option.  ws: ct_icid_workspace_bytes(height, width, batch, downsampling) -- one float64 per 32 x 16 tile of
+ * the map grid; with downsampling off and min(height, width) >= 384 that is MORE than ct_metric_workspace_bytes.
+ * CT_E_BADARG (nothing launched): a null pointer, batch < 0, intent outside 0..2, a map grid smaller than 6 x 6 (reflect padding
+ * of 5).  CT_E_WORKSPACE (nothing launched): no workspace or ws_bytes < ct_icid_workspace_bytes(...).  batch == 0: CT_OK, nothing
+ * launched.                                                                                                                    */
+enum { CT_ICID_PERCEPTUAL = 0, CT_ICID_HUE_PRESERVING = 1, CT_ICID_CHROMATIC = 2 };
+size_t ct_icid_workspace_bytes(int height, int width, int batch, int downsampling);
+int ct_frame_icid_opt_f32(const float *a, const float *b, int height, int width, int batch, int intent, int omit_maps67,
+                          int downsampling, double *out, void *ws, size_t ws_bytes, void *stream);
+int ct_frame_icid_opt_hwc_u8(const float *result_hwc, const uint8_t *gt_hwc, int height, int width, int batch, int intent,
+                             int omit_maps67, int downsampling, double *out, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- a4: methods.iterative.iterative_distribution_transfer (methods/iterative.py:8-59) ----
  * Per iteration: projection on the rotated axes (float64, fma chain), exact lo/hi, 2x3 histograms
  * with numpy's bin rule (LDS-binned integer atomics), cumulative LUT, np.interp apply with the
