@@ -126,6 +126,15 @@ __device__ __forceinline__ void load_tile(const float *tile, int lane, float (&e
         e[3 * j] = a.x; e[3 * j + 1] = a.y; e[3 * j + 2] = a.z;
     }
 }
+// load_tile with the default cache policy: for a tile that another kernel re-reads soon (the targets of a pipelined Reinhard chunk,
+// linear.hip), so that the line may still sit in the Infinity Cache then
+__device__ __forceinline__ void load_tile_plain(const float *tile, int lane, float (&e)[12]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float3v a = *reinterpret_cast<const float3u *>(tile + (j * kWave + lane) * 3);
+        e[3 * j] = a.x; e[3 * j + 1] = a.y; e[3 * j + 2] = a.z;
+    }
+}
 __device__ __forceinline__ void store_tile(float *tile, int lane, const float (&e)[12]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

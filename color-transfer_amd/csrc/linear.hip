@@ -75,21 +75,34 @@ constexpr int kLutMinWaves = 4;
 // A1, float32 arithmetic on the table path (see ct_color_lut.h: statistics only need unbiased per-pixel values): per lane
 // float32 shifted sums over its ~40 pixels, converted once to float64 for the fixed-shape reduction tree.  The exact
 // fallback (out-of-range tiles, the ragged last tile) accumulates in float64 beside it.
+//
+// A launch covers any part of the batch: grid row y stands for image img_lo + y (y < y_split) or img_hi + (y - y_split), and every
+// index into the partials and pivots is the IMAGE's, so a chunk [p0, p1) of a batch of pairs (y_split = p1 - p0, img_lo = p0,
+// img_hi = batch + p0) writes the rows the whole-batch launch (y_split = n_first, img_lo = 0, img_hi = n_first) writes for it.
+// T_PLAIN: the rows below y_split (the targets of a pipelined chunk) are read with the default cache policy -- the apply
+// sweep of the same chunk re-reads them within the reach of the Infinity Cache -- everything else non-temporal as ever.
+template <bool T_PLAIN>
 __global__ __launch_bounds__(kLutBlock, kLutMinWaves) void lab_moments_lut_kernel(const float *__restrict__ base0,
                                                                                   const float *__restrict__ base1, int n_first,
                                                                                   int64_t n_pixels, double *__restrict__ partials,
-                                                                                  double *__restrict__ pivots) {
+                                                                                  double *__restrict__ pivots, int y_split, int img_lo,
+                                                                                  int img_hi) {
     __shared__ __attribute__((aligned(16))) unsigned char tab[lut::kLdsBytesFwd];
     __shared__ double red[kLutWaves * 6];
     __shared__ float piv[3];
-    const int img = blockIdx.y;
+    const int y = blockIdx.y;
+    const int img = (y < y_split) ? img_lo + y : img_hi + (y - y_split);
     const float *p = (img < n_first) ? base0 + (size_t)img * n_pixels * 3 : base1 + (size_t)(img - n_first) * n_pixels * 3;
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t n_full = n_pixels / kTilePixels;                   // full tiles; the ragged rest is swept by workgroup 0
     const int64_t stride = (int64_t)gridDim.x * kLutWaves;
     int64_t t = (int64_t)blockIdx.x * kLutWaves + (threadIdx.x >> 6);
     float cur[12], nxt[12];
-    if (t < n_full) load_tile(p + t * (kTilePixels * 3), lane, cur);          // in flight while the tables are copied
+    auto load = [&](const float *tile, float (&e)[12]) {
+        if (T_PLAIN && y < y_split) load_tile_plain(tile, lane, e);
+        else load_tile(tile, lane, e);
+    };
+    if (t < n_full) load(p + t * (kTilePixels * 3), cur);                     // in flight while the tables are copied
     float p0[3] = {0.f, 0.f, 0.f};
     if (threadIdx.x == 0 && n_pixels > 0) { p0[0] = p[0]; p0[1] = p[1]; p0[2] = p[2]; }
     lut::load_tables<kLutBlock, false>(tab);
@@ -135,7 +148,7 @@ __global__ __launch_bounds__(kLutBlock, kLutMinWaves) void lab_moments_lut_kerne
         }
     };
     for (; t < n_full; t += stride) {
-        if (t + stride < n_full) load_tile(p + (t + stride) * (kTilePixels * 3), lane, nxt);
+        if (t + stride < n_full) load(p + (t + stride) * (kTilePixels * 3), nxt);
         stats_tile(cur);
 #pragma unroll
         for (int i = 0; i < 12; ++i) cur[i] = nxt[i];
@@ -174,12 +187,15 @@ __global__ __launch_bounds__(kLutBlock, kLutMinWaves) void reinhard_apply_lut_ke
                                                                                      const double *__restrict__ partials,
                                                                                      const double *__restrict__ pivots, int n_partials,
                                                                                      int batch, double *__restrict__ stats_out,
-                                                                                     const float *__restrict__ gt, double *__restrict__ sq_partials) {
+                                                                                     const float *__restrict__ gt, double *__restrict__ sq_partials,
+                                                                                     int img0) {
     // gt != NULL: the per-frame squared error of the result against a ground-truth frame (the PSNR of Runner.test_step,
     // methods/__init__.py:32) is accumulated on the way out -- the corrected frame is not read back from HBM for it
+    // img0: the launch covers images img0 .. img0 + gridDim.y - 1 of the batch (a chunk of pairs; 0 = the whole batch); every
+    // pointer and record keeps its whole-batch index
     __shared__ __attribute__((aligned(16))) unsigned char tab[OUT_LAB ? lut::kLdsBytesFwd : lut::kLdsBytesAll];
     __shared__ double fin[12 * 8 + 2 * CT_LAB_STATS_STRIDE];
-    const int img = blockIdx.y;
+    const int img = img0 + blockIdx.y;
     const float *p = target + (size_t)img * n_pixels * 3;
     float *o = out + (size_t)img * n_pixels * 3;
     const int lane = threadIdx.x & (kWave - 1);
@@ -312,6 +328,69 @@ static std::atomic<int> g_lab_mode_default{[] { const char *e = env_str("CT_HIP_
 static thread_local int t_lab_mode = -1;
 static inline int lab_mode() { return t_lab_mode >= 0 ? t_lab_mode : g_lab_mode_default.load(std::memory_order_relaxed); }
 
+// The pipelined form of the fused float32 entries (reinhard_pipelined below; ct_set_reinhard_pipeline): pairs per chunk (-1 = the
+// built-in plan, 0 = off, > 0 forced) and the target-load policy of a chunk's statistics sweep (0 = non-temporal, 1 = plain),
+// packed into one word so that a reader never sees half of a setting.  Two levels like the Lab mode: a process-wide atomic
+// default and a per-thread override (kPipeNoOverride = none); every entry reads it once, on the calling thread.
+// The built-in plan is MEASURED (tools/bench_reinhard_pipeline.py): chunks of about kPlanChunkPixels (four 1080p
+// pairs: 8 pairs of 720p, one of 2160p), an even number of them so that both lanes carry the same load, plain target loads.
+// Frames below kPlanMinPixels and calls below kPlanMinCallPixels keep the two whole-batch launches: there the fork and the
+// join cost as much as the overlap returns.
+constexpr int64_t kPlanChunkPixels = 4 * 1920 * 1080;
+constexpr int64_t kPlanMinPixels = 1280 * 720;
+constexpr int64_t kPlanMinCallPixels = 14000000;
+constexpr int kPlanTPolicy = 1;
+constexpr int kPipeLanes = 2;
+constexpr int kPipeMaxChunk = 1 << 14;
+constexpr int kPipeNoOverride = -2;
+static inline int pipe_pack(int chunk_pairs, int t_policy) { return (chunk_pairs + 2) | (t_policy << 16); }
+static std::atomic<int> g_pipe_default{pipe_pack(-1, kPlanTPolicy)};
+static thread_local int t_pipe_override = kPipeNoOverride;
+static inline void pipe_setting(int *chunk_pairs, int *t_policy) {
+    const int v = t_pipe_override != kPipeNoOverride ? t_pipe_override : g_pipe_default.load(std::memory_order_relaxed);
+    *chunk_pairs = (v & 0xffff) - 2;
+    *t_policy = v >> 16;
+}
+// pairs per chunk this call runs with (0 = the two whole-batch launches)
+static inline int pipe_chunk_for(int chunk_pairs, int64_t n_pixels, int batch) {
+    if (chunk_pairs >= 0) return chunk_pairs;
+    const int64_t total = n_pixels * batch;
+    if (n_pixels < kPlanMinPixels || total < kPlanMinCallPixels || batch < 2) return 0;
+    int64_t half = (total + kPlanChunkPixels) / (2 * kPlanChunkPixels);          // chunks per lane, rounded to nearest
+    if (half < 1) half = 1;
+    const int n_chunks = (int)(kPipeLanes * half < batch ? kPipeLanes * half : batch);
+    return (batch + n_chunks - 1) / n_chunks;
+}
+
+// The second lane of the pipelined form: ONE library-owned stream with its fork / join events, per device and per calling thread,
+// created on first use and kept (the first lane is the caller's own stream).  Non-blocking, so it never synchronises with the
+// legacy default stream behind the caller's back.  NULL when the caller's stream is being captured and the pool does not exist
+// yet (nothing may be created inside a capture: that call stays unpipelined), or when the device refused a stream.
+struct PipePool {
+    hipStream_t st = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    int state = 0;                                  // 0 not tried, 1 ready, -1 failed
+};
+static thread_local PipePool t_pipe_pool[kMaxDevices];
+static PipePool *pipe_pool(hipStream_t s) {
+    PipePool &p = t_pipe_pool[current_device()];
+    if (p.state == 0) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
+        const bool ok = hipStreamCreateWithFlags(&p.st, hipStreamNonBlocking) == hipSuccess &&
+                        hipEventCreateWithFlags(&p.fork, hipEventDisableTiming) == hipSuccess &&
+                        hipEventCreateWithFlags(&p.join, hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (p.join) (void)hipEventDestroy(p.join);
+            if (p.fork) (void)hipEventDestroy(p.fork);
+            if (p.st) (void)hipStreamDestroy(p.st);
+        }
+        p.state = ok ? 1 : -1;
+    }
+    return p.state == 1 ? &p : nullptr;
+}
+
 // Workgroups of a table kernel: ONE round of persistent workgroups -- as many as are resident at once (occupancy query,
 // cached per kernel), each sweeping enough chunks to amortise its 32-37 KB table copy.  CT_HIP_LUT_BLOCKS overrides the
 // total (tuning).
@@ -343,12 +422,12 @@ static int launch_lab_moments(const T *base0, const T *base1, int n_first, int n
                               double *stats, hipStream_t s, int *deferred_partials = nullptr) {
     if (n_images == 0) return CT_OK;
     if constexpr (sizeof(T) == 4) {
-        static const int resident = resident_blocks(lab_moments_lut_kernel);
+        static const int resident = resident_blocks(lab_moments_lut_kernel<false>);
         if (lab_mode() == 0) {
             const int G = lut_blocks_per_image(resident, n_pixels / kTilePixels, n_images);
             if (g_prof_evt[0]) (void)hipEventRecord(g_prof_evt[0], s);
-            hipLaunchKernelGGL(lab_moments_lut_kernel, dim3(G, n_images), dim3(kLutBlock), 0, s, base0, base1, n_first, n_pixels,
-                               l.partials, l.pivots);
+            hipLaunchKernelGGL(lab_moments_lut_kernel<false>, dim3(G, n_images), dim3(kLutBlock), 0, s, base0, base1, n_first, n_pixels,
+                               l.partials, l.pivots, n_first, 0, n_first);
             CT_CHECK_LAUNCH();
             if (g_prof_evt[1]) (void)hipEventRecord(g_prof_evt[1], s);
             if (deferred_partials != nullptr && n_pixels > 0) {
@@ -383,7 +462,7 @@ static int launch_reinhard_apply(const T *target, const double *st, const double
         if (use_lut)
             hipLaunchKernelGGL((reinhard_apply_lut_kernel<OUT_LAB>), dim3(G, batch), dim3(kLutBlock), 0, s, target, st, sr, out,
                                n_pixels, (const double *)(deferred ? deferred->partials : nullptr),
-                               (const double *)(deferred ? deferred->pivots : nullptr), n_partials, batch, stats_out, gt, sq_partials);
+                               (const double *)(deferred ? deferred->pivots : nullptr), n_partials, batch, stats_out, gt, sq_partials, 0);
         if (use_lut && sq_blocks) *sq_blocks = G;
     }
     if (!use_lut)
@@ -437,6 +516,54 @@ static int reinhard_f64_impl(const double *target, const double *reference, doub
 // Workspace of the fused entry with the PSNR: the Reinhard layout followed by batch x kMaxBlocksPerImage doubles.
 static size_t ws_bytes_reinhard_psnr(int batch) { return ws_bytes_for(2 * batch) + (size_t)batch * kMaxBlocksPerImage * sizeof(double); }
 
+// The two table sweeps over chunks of `chunk` pairs on two lanes: chunk k runs statistics(k) -> apply(k) on the caller's stream (even
+// k) or on the library's stream (odd k), which is forked from the caller's stream with an event before the first chunk and
+// joined back into it with an event after the last -- no kernel waits for another, only stream order.  Every chunk launch is sized
+// for 1 / kPipeLanes of the chip, so the kernels of the two lanes are resident SIDE BY SIDE: one lane's ramp (32-37 KB of tables
+// per workgroup, the prologue barriers) and drain run under the other lane's streaming, and a statistics sweep (arithmetic and
+// streaming in balance) shares the CUs with an apply sweep (HBM bound) whenever the lanes are out of phase.  Measured against
+// the alternatives: whole-chip grids only overlap a tail with a ramp, and two library streams beside an idle
+// caller's stream pay a second fork and join (slower than the whole-batch launches).
+// The per-image workgroup counts are those of a FULL chunk, for the ragged last chunk too: one count of squared-error partials per
+// image for the PSNR finish, and a static tile -> workgroup map.  Chunks write disjoint rows of the workspace and the order in
+// which the lanes happen to run enters no sum: results are bitwise reproducible run to run.  The PSNR finish stays with the
+// caller (once, over all images, on `s`).  Capturable: the fork / join events make the second lane part of a capture of `s`.
+static int reinhard_pipelined(const float *target, const float *reference, const float *gt, float *out, int64_t n_pixels, int batch,
+                              double *stats, const WsLayout &l, double *sq, int *sq_blocks, int chunk, bool t_plain, PipePool &pp,
+                              hipStream_t s) {
+    static const int res_stats = resident_blocks(lab_moments_lut_kernel<false>);
+    static const int res_apply = resident_blocks(reinhard_apply_lut_kernel<false>);
+    if (chunk > batch) chunk = batch;
+    const int64_t tiles = n_pixels / kTilePixels;
+    const int Gs = lut_blocks_per_image(res_stats / kPipeLanes, tiles, 2 * chunk);
+    const int Ga = lut_blocks_per_image(res_apply / kPipeLanes, tiles, chunk);
+    hipError_t e = hipEventRecord(pp.fork, s);
+    if (e != hipSuccess) return (int)e;             // nothing forked yet
+    e = hipStreamWaitEvent(pp.st, pp.fork, 0);
+    int k = 0;
+    for (int p0 = 0; p0 < batch && e == hipSuccess; p0 += chunk, ++k) {
+        const int cp = batch - p0 < chunk ? batch - p0 : chunk;
+        hipStream_t q = (k & 1) ? pp.st : s;
+        if (t_plain)
+            hipLaunchKernelGGL(lab_moments_lut_kernel<true>, dim3(Gs, 2 * cp), dim3(kLutBlock), 0, q, target, reference, batch, n_pixels,
+                               l.partials, l.pivots, cp, p0, batch + p0);
+        else
+            hipLaunchKernelGGL(lab_moments_lut_kernel<false>, dim3(Gs, 2 * cp), dim3(kLutBlock), 0, q, target, reference, batch, n_pixels,
+                               l.partials, l.pivots, cp, p0, batch + p0);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        hipLaunchKernelGGL((reinhard_apply_lut_kernel<false>), dim3(Ga, cp), dim3(kLutBlock), 0, q, target, (const double *)stats,
+                           (const double *)(stats + (size_t)batch * CT_LAB_STATS_STRIDE), out, n_pixels, (const double *)l.partials,
+                           (const double *)l.pivots, Gs, batch, stats, gt, sq, p0);
+        e = hipGetLastError();
+    }
+    // join even after an error: a capture of `s` must not be left with a forked stream
+    hipError_t j = hipEventRecord(pp.join, pp.st);
+    if (j == hipSuccess) j = hipStreamWaitEvent(s, pp.join, 0);
+    if (e == hipSuccess) e = j;
+    if (gt != nullptr) *sq_blocks = Ga;
+    return (int)e;
+}
+
 // a1 for float32 frames, the body of ct_reinhard_f32 (psnr = false; gt, psnr_out NULL) and of ct_reinhard_psnr_f32: the latter is
 // color_transfer_between_images for `batch` pairs fused with the per-frame PSNR of Runner.test_step (methods/__init__.py:30-32,37),
 // PSNR(result, gt) per frame.  Past the argument checks gt != NULL means "with the PSNR".  Table path: the squared error is
@@ -468,12 +595,25 @@ static int reinhard_f32_impl(bool psnr, const float *target, const float *refere
         }
         rc = reinhard_separate_sweeps(target, reference, gt, out, n_pixels, batch, stats, l, sq, &sq_blocks, s);      // e.g. out == target
     } else {
-        // one sweep over all 2*batch images; stats records [0,batch) = targets, [batch,2batch) = references
-        int deferred = 0;      // > 0: table path, the apply kernel finishes the statistics in its prologue (and writes stats_out)
-        rc = launch_lab_moments<float>(target, reference, batch, 2 * batch, n_pixels, l, stats, s, &deferred);
-        if (rc) return rc;
-        rc = launch_reinhard_apply<float, false>(target, stats, stats + (size_t)batch * CT_LAB_STATS_STRIDE, out, n_pixels, batch, s,
-                                                 deferred > 0 ? &l : nullptr, deferred, stats, deferred > 0 ? gt : nullptr, sq, &sq_blocks);
+        // Table arithmetic, no profile events armed (they bracket undisturbed whole-batch launches), `out` clear of every input
+        // (out == target exactly is fine: a chunk's apply sweep writes only its own targets): the sweeps may run chunk by chunk
+        int chunk_pairs, t_policy;
+        pipe_setting(&chunk_pairs, &t_policy);
+        const int chunk = pipe_chunk_for(chunk_pairs, n_pixels, batch);
+        PipePool *pp = nullptr;
+        if (chunk > 0 && lab_mode() == 0 && n_pixels > 0 && !g_prof_evt[0] && !g_prof_evt[1] && !g_prof_evt[2] && !g_prof_evt[3] &&
+            !rp::overlaps(out, out == target ? nullptr : target, reference, gt, n_pixels, batch, sizeof(float)))
+            pp = pipe_pool(s);
+        if (pp != nullptr) {
+            rc = reinhard_pipelined(target, reference, gt, out, n_pixels, batch, stats, l, sq, &sq_blocks, chunk, t_policy == 1, *pp, s);
+        } else {
+            // one sweep over all 2*batch images; stats records [0,batch) = targets, [batch,2batch) = references
+            int deferred = 0;      // > 0: table path, the apply kernel finishes the statistics in its prologue (and writes stats_out)
+            rc = launch_lab_moments<float>(target, reference, batch, 2 * batch, n_pixels, l, stats, s, &deferred);
+            if (rc) return rc;
+            rc = launch_reinhard_apply<float, false>(target, stats, stats + (size_t)batch * CT_LAB_STATS_STRIDE, out, n_pixels, batch, s,
+                                                     deferred > 0 ? &l : nullptr, deferred, stats, deferred > 0 ? gt : nullptr, sq, &sq_blocks);
+        }
     }
     if (rc || gt == nullptr) return rc;
     if (sq_blocks == 0) {                       // exact path: a sweep of its own over (out, gt)
@@ -514,6 +654,33 @@ int ct_set_lab_mode_thread(int mode) {
     if (mode != -1 && mode != CT_LAB_TABLE && mode != CT_LAB_EXACT) return CT_E_BADARG;
     ct::t_lab_mode = mode;
     return CT_OK;
+}
+
+static bool pipe_args_ok(int chunk_pairs, int t_policy) {
+    return chunk_pairs >= -1 && chunk_pairs <= ct::kPipeMaxChunk && t_policy >= -1 && t_policy <= CT_PIPE_T_PLAIN;
+}
+int ct_set_reinhard_pipeline(int chunk_pairs, int t_policy) {
+    if (!pipe_args_ok(chunk_pairs, t_policy)) return CT_E_BADARG;
+    ct::g_pipe_default.store(ct::pipe_pack(chunk_pairs, t_policy < 0 ? ct::kPlanTPolicy : t_policy), std::memory_order_relaxed);
+    return CT_OK;
+}
+int ct_set_reinhard_pipeline_thread(int chunk_pairs, int t_policy) {
+    if (chunk_pairs == ct::kPipeNoOverride) { ct::t_pipe_override = ct::kPipeNoOverride; return CT_OK; }
+    if (!pipe_args_ok(chunk_pairs, t_policy)) return CT_E_BADARG;
+    ct::t_pipe_override = ct::pipe_pack(chunk_pairs, t_policy < 0 ? ct::kPlanTPolicy : t_policy);
+    return CT_OK;
+}
+int ct_get_reinhard_pipeline(int *chunk_pairs, int *t_policy) {
+    int c, p;
+    ct::pipe_setting(&c, &p);
+    if (chunk_pairs) *chunk_pairs = c;
+    if (t_policy) *t_policy = p;
+    return CT_OK;
+}
+int ct_reinhard_pipeline_chunk(int64_t n_pixels, int batch) {
+    int c, p;
+    ct::pipe_setting(&c, &p);
+    return ct::pipe_chunk_for(c, n_pixels, batch);
 }
 
 void ct_profile_events(void *moments_start, void *moments_stop, void *apply_start, void *apply_stop) {

@@ -16,9 +16,10 @@ from ._core import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SW
                     CT_LAB_STATS_STRIDE, CT_RGB_STATS_STRIDE, CT_WS_IDT, CT_WS_LAB_STATS, CT_WS_MK_U8, CT_WS_REINHARD, CT_WS_REINHARD_PERSIST,
                     CT_WS_REINHARD_PSNR, CT_WS_RGB_MEANCOV, CtHipError, LIB_PATH, SIGNATURES, check, device_status, lib,
                     workspace, _stream)
-from .linear import (CT_LAB_EXACT, CT_LAB_TABLE, affine3x3, lab_mode, lab_stats, mk, mk_coef, profile_events, reinhard,
-                     reinhard_apply, reinhard_persist, reinhard_persist_supported, reinhard_psnr, reinhard_takes_persist,
-                     rgb_meancov, set_lab_mode, upload_records)
+from .linear import (CT_LAB_EXACT, CT_LAB_TABLE, CT_PIPE_T_NT, CT_PIPE_T_PLAIN, affine3x3, lab_mode, lab_stats, mk, mk_coef,
+                     profile_events, reinhard, reinhard_apply, reinhard_persist, reinhard_persist_supported, reinhard_pipeline,
+                     reinhard_pipeline_chunk, reinhard_psnr, reinhard_takes_persist, rgb_meancov, set_lab_mode,
+                     set_reinhard_pipeline, upload_records)
 from .metrics import (CT_WS_FSIM, DISTORTIONS, ICID_INTENTS, icid_intent, distort_u8, fft2d_, frame_fsim, frame_fsim_hwc, frame_icid, frame_icid_hwc, frame_psnr, frame_ssim,
                       frame_ssim_hwc, regrain,
                       _fsim_stages, _fsim_tables)

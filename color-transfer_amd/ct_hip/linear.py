@@ -14,6 +14,10 @@ SIGNATURES.update({
     "ct_set_lab_mode": (_c_int, [_c_int]),
     "ct_get_lab_mode": (_c_int, []),
     "ct_set_lab_mode_thread": (_c_int, [_c_int]),
+    "ct_set_reinhard_pipeline": (_c_int, [_c_int, _c_int]),
+    "ct_set_reinhard_pipeline_thread": (_c_int, [_c_int, _c_int]),
+    "ct_get_reinhard_pipeline": (_c_int, [_c_p, _c_p]),
+    "ct_reinhard_pipeline_chunk": (_c_int, [_c_i64, _c_int]),
     "ct_lab_stats_f32": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
     "ct_lab_stats_f64": (_c_int, [_c_p, _c_i64, _c_int, _c_p, _c_p, _c_sz, _c_p]),
     "ct_reinhard_apply_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
@@ -59,6 +63,36 @@ def set_lab_mode(mode, thread=False):
 
 def lab_mode():
     return "exact" if lib().ct_get_lab_mode() == CT_LAB_EXACT else "table"
+
+
+CT_PIPE_T_NT, CT_PIPE_T_PLAIN = 0, 1
+
+
+def set_reinhard_pipeline(chunk_pairs, t_policy=-1, thread=False):
+    """The float32 Reinhard sweeps over chunks of pairs on the caller's stream and a library-owned one (include/ct_hip.h: ct_set_reinhard_pipeline).
+    chunk_pairs: -1 the built-in plan, 0 off, > 0 forced at any frame size and batch; t_policy: "nt" / "plain" (or the codes; -1 =
+    the built-in choice) for the target tiles of a chunk's statistics sweep.  Process-wide, or -- thread=True -- for the calling
+    thread only (chunk_pairs None removes that override)."""
+    if thread and chunk_pairs is None:
+        check(lib().ct_set_reinhard_pipeline_thread(-2, -1))
+        return
+    code = {"nt": CT_PIPE_T_NT, "plain": CT_PIPE_T_PLAIN}.get(t_policy, t_policy)
+    if code not in (-1, CT_PIPE_T_NT, CT_PIPE_T_PLAIN):
+        raise ValueError("target-load policy must be 'nt', 'plain' or -1, got %r" % (t_policy,))
+    fn = lib().ct_set_reinhard_pipeline_thread if thread else lib().ct_set_reinhard_pipeline
+    check(fn(int(chunk_pairs), code))
+
+
+def reinhard_pipeline():
+    """(chunk_pairs, t_policy code) the calling thread's next reinhard() / reinhard_psnr() call reads"""
+    c, p = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().ct_get_reinhard_pipeline(ctypes.byref(c), ctypes.byref(p)))
+    return c.value, p.value
+
+
+def reinhard_pipeline_chunk(n_pixels, batch):
+    """Pairs per chunk the current setting gives float32 frames of n_pixels in a call of `batch` pairs (0 = the whole-batch launches)"""
+    return int(lib().ct_reinhard_pipeline_chunk(int(n_pixels), int(batch)))
 
 
 def profile_events(events):
@@ -142,9 +176,10 @@ def reinhard(target, reference, out=None, stats_out=None):
     return out.view(target.shape)
 
 
-def reinhard_psnr(target, reference, gt, out=None, psnr_out=None):
+def reinhard_psnr(target, reference, gt, out=None, psnr_out=None, stats_out=None):
     """color_transfer_between_images for B float32 pairs + the per-frame PSNR of the result against `gt` (same layout as the
-    images), as Runner.test_step computes it (methods/__init__.py:30-32).  Returns (out, psnr float64 [B, 2] = mse, PSNR)."""
+    images), as Runner.test_step computes it (methods/__init__.py:30-32).  Returns (out, psnr float64 [B, 2] = mse, PSNR).
+    stats_out: float64, >= 2*B*8 elements, receives the Lab records (targets, then references) like reinhard()'s."""
     x, _ = _as_batch(target)
     r, _ = _as_batch(reference)
     g, _ = _as_batch(gt)
@@ -156,9 +191,13 @@ def reinhard_psnr(target, reference, gt, out=None, psnr_out=None):
         out = torch.empty_like(x)
     if psnr_out is None:
         psnr_out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    if stats_out is not None:
+        _require_cuda(stats_out)
+        if stats_out.dtype != torch.float64 or stats_out.numel() < 2 * B * CT_LAB_STATS_STRIDE:
+            raise CtHipError("stats_out must be float64 with >= 2*B*8 elements")
+    sp = _ptr(stats_out) if stats_out is not None else ctypes.c_void_p(0)
     ws = workspace(CT_WS_REINHARD_PSNR, n, B, x.device)
-    check(lib().ct_reinhard_psnr_f32(_ptr(x), _ptr(r), _ptr(g), _ptr(out), _ptr(psnr_out), n, B, ctypes.c_void_p(0), _ptr(ws), ws.numel(),
-                                     _stream()))
+    check(lib().ct_reinhard_psnr_f32(_ptr(x), _ptr(r), _ptr(g), _ptr(out), _ptr(psnr_out), n, B, sp, _ptr(ws), ws.numel(), _stream()))
     return out.view(target.shape), psnr_out
 
 

@@ -79,6 +79,28 @@ int ct_device_status(int clear);
 int ct_set_lab_mode(int mode);
 int ct_set_lab_mode_thread(int mode);
 int ct_get_lab_mode(void);
+/* The two table sweeps of ct_reinhard_f32 / ct_reinhard_psnr_f32 over CHUNKS of pairs (entries added under ABI 9, no argument list
+ * changed): chunk k runs statistics(k) -> apply(k) on the caller's stream (even k) or on a library-owned non-blocking stream (odd k;
+ * one per device and per calling thread, created on first use outside a stream capture and kept), which is forked from the
+ * caller's stream with an event and joined back into it with an event; each launch is sized for half the chip, so the kernels
+ * of the two lanes are resident side by side and one lane's ramp and drain run under the other's streaming.  The PSNR finish
+ * runs once on the caller's stream.  Capturable in a graph once the stream exists (a first call inside a capture stays unpipelined).
+ *   chunk_pairs  -1 the built-in plan (measured, DESIGN.md 4.1: chunks of about four pairs for calls of >= 8 pairs of >= 2 Mpixel,
+ *                the whole-batch launches below), 0 off, > 0 that many pairs per chunk at any frame size and batch (tests, tuning);
+ *   t_policy     how the statistics sweep of a chunk reads its TARGET tiles, which the chunk's apply sweep re-reads:
+ *                CT_PIPE_T_NT non-temporal like every other access, CT_PIPE_T_PLAIN default cache policy; -1 = the built-in choice.
+ * Whatever the setting, the two whole-batch launches are kept for CT_LAB_EXACT, float64 frames, an `out` that overlaps an input
+ * other than out == target exactly, and while ct_profile_events is armed.  Results: bitwise reproducible run to run for a given
+ * setting; against the whole-batch launches only the grouping of the statistics' partial sums differs (as it already does
+ * between batch sizes).  ct_set_reinhard_pipeline: process-wide default (atomic); ct_set_reinhard_pipeline_thread: an override
+ * for the CALLING thread (chunk_pairs -2 removes it); ct_get_reinhard_pipeline: the setting the calling thread's next call reads;
+ * ct_reinhard_pipeline_chunk: the pairs per chunk that setting gives frames of n_pixels in a call of `batch` pairs (0 = whole batch). */
+#define CT_PIPE_T_NT 0
+#define CT_PIPE_T_PLAIN 1
+int ct_set_reinhard_pipeline(int chunk_pairs, int t_policy);
+int ct_set_reinhard_pipeline_thread(int chunk_pairs, int t_policy);
+int ct_get_reinhard_pipeline(int *chunk_pairs, int *t_policy);
+int ct_reinhard_pipeline_chunk(int64_t n_pixels, int batch);
 /* Measurement hook: four hipEvent_t (or NULL = off) that the library records on the launch stream immediately before /
  * after moments_kernel<T,true> and reinhard_apply_kernel of the following ct_lab_stats / ct_reinhard* calls, so that a
  * caller can time exactly those kernels with hipEventElapsedTime (bench.py `roofline`).  When a call takes the persistent
