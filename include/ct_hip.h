@@ -919,6 +919,37 @@ int ct_pam_map_sweep_f32(const float *att, const float *src, const float *dst, c
 int ct_masked_l1_f32(const float *x, const float *y, const float *mask, double *out, void *ws, size_t ws_bytes, int n, int64_t a,
                      int64_t p, int64_t b, void *stream);
 
+/* ---- perspective warp of uint8 frames (utils/postprocess.py:97 cv2.flip(left, 1); :127-136 crop to bbox, cv2.warpPerspective
+ * with INTER_LINEAR and a constant 0 border, dsize = the crop's own size, second crop; csrc/warp.hip) ------------------------
+ * raw: uint8 [n][src_h][src_w][3]; out: uint8 [n][out_h][out_w][3].  The source image of the warp is the crop
+ * (crop_x, crop_y, crop_w, crop_h) of the raw frame -- with flip_x != 0 of the raw frame mirrored left-right,
+ * raw[r][src_w - 1 - c] -- and a tap outside the crop is 0 even where the raw frame has pixels.  The destination is
+ * crop_w x crop_h; only its window (out_x, out_y, out_w, out_h) is computed and stored.
+ * maps: device float64 [n][9], or [9] with shared != 0: the DESTINATION -> SOURCE matrix, row-major (cv2's M after its own
+ * invert; inverting is the caller's job).
+ * The rule is OpenCV's fixed-point bilinear path (imgwarp.cpp up to 4.10, INTER_BITS = 5) restated; parity unpinned: cv2 is
+ * absent offline, no version is pinned, and OpenCV 4.11 replaced the path with a float one.  For destination (row r, column c):
+ *   bh0 = min(16, crop_h), bw0 = min(1024 / bh0, crop_w), x0 = (c / bw0) * bw0, x1 = c - x0;
+ *   float64, one rounding per operation, no fma, left to right:
+ *   X0 = M0*x0 + M1*r + M2;  Y0 = M3*x0 + M4*r + M5;  W0 = M6*x0 + M7*r + M8
+ *   W  = W0 + M6*x1;  W = (W != 0) ? 32 / W : 0
+ *   fX = max(-2^31, min(2^31 - 1, (X0 + M0*x1) * W)), fY likewise with M3;  X = (int)rint(fX) (ties to even), Y likewise
+ *   sx = sat16(X >> 5), sy = sat16(Y >> 5), a = X & 31, b = Y & 31
+ *   out = ((32-a)(32-b) p[sy][sx] + a(32-b) p[sy][sx+1] + (32-a)b p[sy+1][sx] + ab p[sy+1][sx+1] + 512) >> 10   per channel.
+ * path: CT_WARP_AUTO / CT_WARP_GLOBAL read every tap from memory (the faster one at 1080p), CT_WARP_STAGED stages each tile's
+ * source rows in LDS (raw and its row pitch on the 16-byte grid, else global taps); the bytes are the same.  out may have any alignment and width: of every
+ * row of a tile the 16-byte runs on the grid leave as vector stores, the up to 15 bytes at either end element-wise.
+ * Memory-safe for ANY matrix (taps are bounds-checked after the integer conversion); with non-finite entries the pixel
+ * values are unspecified.  Deterministic, no workspace.
+ * CT_E_BADARG, before anything is launched: a null pointer, any size < 1, crop_w or crop_h > 32767, a crop that is not inside the
+ * raw frame, a window that is not inside the destination, an unknown path.  CT_E_ALIGN: maps off 8 bytes.  Added under ABI 9. */
+#define CT_WARP_AUTO 0
+#define CT_WARP_STAGED 1
+#define CT_WARP_GLOBAL 2
+int ct_warp_perspective_u8(const uint8_t *raw, int n, int src_h, int src_w, int flip_x, int crop_x, int crop_y, int crop_w,
+                           int crop_h, const double *maps, int shared, int out_x, int out_y, int out_w, int out_h, uint8_t *out,
+                           int path, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
