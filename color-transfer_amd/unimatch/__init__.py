@@ -380,6 +380,37 @@ class GMFlow(nn.Module):
         mask = _conv(self.refine.mask[2], _conv(self.refine.mask[0], h, ACT_RELU)) if want_mask else None
         return h, mask, delta
 
+    def _global_match(self, t0, t1, h, w, bidir):                         # matching.py:10-39, both directions
+        """global matching as attention over a coordinate table: softmax(t0 t1^T / sqrt(c)) grid - grid, [b or 2b, 2, h, w]"""
+        grid = _coords_tokens(t0.shape[0], h, w, t0.device)
+        fwd = ct_hip.attention_tokens(t0, t1, grid)
+        if bidir:
+            bwd = ct_hip.attention_tokens(t1, t0, grid)
+            corresp = torch.cat((fwd, bwd), dim=0)
+            grid2 = torch.cat((grid, grid), dim=0)
+        else:                                                             # matching.py:27-39 without the transposed half
+            corresp, grid2 = fwd, grid
+        return _nchw(ct_hip.eltwise(0, corresp, ct_hip.eltwise(4, grid2, s0=-1.0)), h, w)
+
+    def _propagate(self, t0, flow, h, w, prop_r):                         # attention.py:188-256
+        prop = self.feature_flow_attn
+        qtok = _lin(prop.q_proj, t0)
+        if prop_r <= 0:
+            ktok = _lin(prop.k_proj, qtok)                                # k_proj(q_proj(x)): the reference's documented quirk
+            return _nchw(ct_hip.attention_tokens(qtok, ktok, _tokens(flow)), h, w)
+        return ct_hip.local_attn_prop(qtok, _lin(prop.k_proj, t0), flow.contiguous(), prop_r)
+
+    def _refine_state(self, t0, h, w):                                    # unimatch.py:318-323
+        """(net, x buffer with inp in its first 128 channels, the GRU's loop-invariant partial sums or None)"""
+        proj = ct_hip.eltwise(5, _conv(self.refine_proj, _nchw(t0, h, w)), plane=h * w, chans=256, split=128)
+        net0 = proj[:, :128].contiguous()                                            # loop invariant (unimatch.py:318-323)
+        xbuf = torch.empty((proj.shape[0], 256, h, w), dtype=torch.float32, device=proj.device)
+        xbuf[:, :128] = proj[:, 128:]                                                # inp; [128:254] motion features, [254:] flow
+        # split mode: the invariant input blocks of the GRU convolutions are convolved once (8 of the 18 block
+        # convolutions of an iteration); exact mode keeps the reference's form
+        pre = self._gru_invariants(net0, xbuf[:, :128]) if ct_hip.conv_mode() == "split" and w % 4 == 0 else None
+        return net0, xbuf, pre
+
     @torch.no_grad()
     def _unimatch(self, img0, img1, num_reg_refine, dbg, bidir=True):    # unimatch.py:98-370 (fixed configuration)
         B = img0.shape[0]
@@ -402,16 +433,8 @@ class GMFlow(nn.Module):
             t0, t1 = self._transformer(_tokens(f0), _tokens(f1), h, w, splits)
             if dbg is not None:
                 dbg["tf0_s%d" % scale] = _nchw(t0, h, w)
-            if corr_r == -1:                                              # matching.py:10-39, both directions
-                grid = _coords_tokens(b, h, w, f0.device)
-                fwd = ct_hip.attention_tokens(t0, t1, grid)
-                if bidir:
-                    bwd = ct_hip.attention_tokens(t1, t0, grid)
-                    corresp = torch.cat((fwd, bwd), dim=0)
-                    grid2 = torch.cat((grid, grid), dim=0)
-                else:                                                     # matching.py:27-39 without the transposed half
-                    corresp, grid2 = fwd, grid
-                pred = _nchw(ct_hip.eltwise(0, corresp, ct_hip.eltwise(4, grid2, s0=-1.0)), h, w)
+            if corr_r == -1:
+                pred = self._global_match(t0, t1, h, w, bidir)
             else:
                 pred = ct_hip.local_corr_softmax(t0, t1, h, w, corr_r)
             flow = ct_hip.eltwise(0, flow, pred) if flow is not None else pred
@@ -419,24 +442,12 @@ class GMFlow(nn.Module):
                 dbg["flow_match_s%d" % scale] = flow
             if scale == 0 and bidir:
                 t0 = torch.cat((t0, t1), dim=0)
-            prop = self.feature_flow_attn                                 # attention.py:188-256
-            qtok = _lin(prop.q_proj, t0)
-            if prop_r <= 0:
-                ktok = _lin(prop.k_proj, qtok)                            # k_proj(q_proj(x)): the reference's documented quirk
-                flow = _nchw(ct_hip.attention_tokens(qtok, ktok, _tokens(flow)), h, w)
-            else:
-                flow = ct_hip.local_attn_prop(qtok, _lin(prop.k_proj, t0), flow.contiguous(), prop_r)
+            flow = self._propagate(t0, flow, h, w, prop_r)
             if dbg is not None:
                 dbg["flow_prop_s%d" % scale] = flow
             if scale == 1:
                 t0_ori, t1_ori = _tokens(f0_ori), _tokens(f1_ori)
-                proj = ct_hip.eltwise(5, _conv(self.refine_proj, _nchw(t0, h, w)), plane=h * w, chans=256, split=128)
-                net0 = proj[:, :128].contiguous()                                        # loop invariant (unimatch.py:318-323)
-                xbuf = torch.empty((proj.shape[0], 256, h, w), dtype=torch.float32, device=proj.device)
-                xbuf[:, :128] = proj[:, 128:]                                            # inp; [128:254] motion features, [254:] flow
-                # split mode: the invariant input blocks of the GRU convolutions are convolved once (8 of the 18 block
-                # convolutions of an iteration); exact mode keeps the reference's form
-                pre = self._gru_invariants(net0, xbuf[:, :128]) if ct_hip.conv_mode() == "split" and w % 4 == 0 else None
+                net0, xbuf, pre = self._refine_state(t0, h, w)
                 for it in range(num_reg_refine):
                     corr = ct_hip.local_corr_flow(t0_ori, t1_ori, flow, 4)
                     last = it == num_reg_refine - 1
