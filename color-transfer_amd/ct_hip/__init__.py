@@ -44,6 +44,7 @@ from .png import INFLATE_STATUS, PNG_MAX_WIDTH, PNG_ROWS_PER_CHUNK, inflate, png
 from .augment import AUGMENT_KINDS, AUGMENT_MAX_OPS, AUGMENT_SAMPLE, augment_table, augment_u8, frame_losses
 from .pam_losses import PAM_SWEEP_MAX_W, masked_l1_sums, pam_cycle_l1, pam_map_sweep
 from .warp import CT_WARP_AUTO, CT_WARP_GLOBAL, CT_WARP_STAGED, WARP_MAX_SIDE, WARP_PATHS, invert3x3, warp_maps, warp_perspective
+from .yuv import YUV_MATRICES, YUV_RANGES, YUV_SITINGS, rgb_to_yuv420, yuv420_frame_bytes, yuv420_to_rgb
 from . import _core
 
 

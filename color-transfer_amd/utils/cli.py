@@ -1,5 +1,5 @@
 """`python -m utils.cli test --config <yaml> [--model.func_spec ...] [--data.n_frames N] [--ckpt_path P]`
-`python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|null] [--views a,b,c] [--writer.depth D] [--writer.workers N] [--writer.png_encoder host|device] [...]`
+`python -m utils.cli predict --config <yaml> --output DIR [--format png|npy|raw|y4m|null] [--views a,b,c] [--writer.depth D] [--writer.workers N] [--writer.png_encoder host|device] [...]`
 both with `[--inference.scale_factor S] [--inference.antialias B]`
 `python -m utils.cli validate --config <yaml> [--ckpt_path P] [--data.synthetic trainval] [--data.crop_size [H,W]] [--data.image_repeats R] [--data.batch_size B] [--seed_everything N]`
 
@@ -45,6 +45,16 @@ and unfiltered on the GPU (ct_hip.png_decode, csrc/png_decode.hip), N samples' f
 utils.data.prefetch_decoded); what the device decoder does not take (anything but 8-bit RGB without interlace) is decoded by PIL as
 before, file by file.  Under CT_CLI_DEVICE=cpu it is refused before the first frame.  The default is `host`: nothing changes.
 
+`--data.y4m_target T.y4m --data.y4m_reference R.y4m [--data.y4m_gt G.y4m] [--data.yuv_matrix bt709|bt601] [--data.yuv_range limited|full]`
+(test, predict) and `--data.synthetic video_yuv`: stereo video as 8-bit Y'CbCr 4:2:0 (utils.data.StereoY4MVideo over Y4M files, the
+stand-in for the reference's cv2.VideoCapture; or synthetic I420 chunks).  The frames are uploaded as YUV, 1.5 bytes per pixel, and a
+whole group is converted by one ct_hip.yuv420_to_rgb launch into the uint8 RGB group every grouped method takes.  Without `y4m_gt`,
+`predict` works and `test` is refused before the first frame.  `predict --format y4m [--writer.y4m_fps 25:1] [--writer.y4m_aspect 1:1]`:
+the corrected frames leave as ONE file `frames.y4m` (ct_hip.rgb_to_yuv420 on the device, 1.5 bytes per pixel downloaded), by
+definition the YUV of the bytes `--format png` would have written; with a Y4M input the rate, aspect, siting and range are inherited
+from it, the matrix from `--data.yuv_matrix`.  Not with `--views`.  Under CT_CLI_DEVICE=cpu the format and the YUV datasets are refused
+before the first frame.
+
 `--model.byte_groups true`, `--model.iterative_groups true`, `--model.grading_groups true` (test, predict; `Runner` with
 `--model.metrics psnr` on a loader of uint8 groups): MK and Xiao, the iterative distribution transfer, automated colour grading take a
 whole group of uint8 frames per call (`Runner.takes_groups()`, `test_group`, `predict_group`) instead of one float32 frame.  Each flag
@@ -85,7 +95,8 @@ def _set(cfg, dotted, value):
         if k in ("model", "data") and keys[-1] != "class_path":
             node = node.setdefault("init_args", {})
             in_init = True
-    node[keys[-1]] = yaml.safe_load(value)
+    # a ratio like 25:1 is a sexagesimal integer to YAML 1.1: these keys keep their text
+    node[keys[-1]] = value if keys[-1] in ("y4m_fps", "y4m_aspect") else yaml.safe_load(value)
 
 
 def _instantiate(section):
@@ -130,8 +141,8 @@ def _view_names(value, fmt):
         raise SystemExit("--views: unknown view %s; the views are %s" % (", ".join(map(repr, bad)), ", ".join(ALL_VIEWS)))
     if len(set(names)) != len(names):
         raise SystemExit("--views %r names a view twice" % (value,))
-    if fmt == "raw":
-        raise SystemExit("--views does not go with --format raw: a raw video is one file with one image per frame; use png or npy")
+    if fmt in ("raw", "y4m"):
+        raise SystemExit("--views does not go with --format %s: a %s video is one file with one image per frame; use png or npy" % (fmt, fmt))
     return names
 
 
@@ -293,6 +304,9 @@ def main(argv=None, timing=None):
             raise SystemExit("predict needs `--output DIR`: the directory the corrected frames are written to")
         if opts.setdefault("format", "png") not in FORMATS:
             raise SystemExit("--format %r: one of %s" % (opts["format"], ", ".join(FORMATS)))
+        if opts["format"] == "y4m" and os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
+            raise SystemExit("--format y4m needs a GPU: the frames are converted on the device (ct_hip.rgb_to_yuv420); under "
+                             "CT_CLI_DEVICE=cpu there is none; use png, npy or raw")
         views = _view_names(opts["views"], opts["format"]) if "views" in opts else None
         from utils.writer import PNG_ENCODERS
         encoder = (cfg.get("writer") or {}).get("png_encoder", "host")
@@ -308,6 +322,10 @@ def main(argv=None, timing=None):
     if decoder == "device" and os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
         raise SystemExit("--data.png_decoder device needs a GPU: under CT_CLI_DEVICE=cpu the frames are host tensors and there "
                          "is no device to decode on; use the default `host` decoder")
+    data_args = (cfg.get("data") or {}).get("init_args") or {}
+    if (data_args.get("y4m_target") or data_args.get("synthetic") == "video_yuv") and os.environ.get("CT_CLI_DEVICE", "cuda") == "cpu":
+        raise SystemExit("--data.y4m_target / --data.synthetic video_yuv need a GPU: the frames are converted on the device "
+                         "(ct_hip.yuv420_to_rgb); there is no CT_CLI_DEVICE=cpu stand-in")
     ctx = _setup(cfg, ckpt, validate=argv[0] == "validate")
     import torch.distributed as dist
     try:
@@ -332,6 +350,9 @@ def _test(ctx, timing):
     # the reference's test_dataloader() returns [artificial, real-world] (utils/data.py:168-179) and Lightning logs each
     # metric once per loader ("Test PSNR/dataloader_idx_1"); a single loader prints the bare names like Lightning does
     tables = []
+    for frames in loaders:
+        if getattr(frames, "has_gt", True) is False:        # before the first frame
+            raise SystemExit("test needs a ground truth: pass --data.y4m_gt (without it only `predict` works)")
     for li, frames in enumerate(loaders):
         mine = sh.frames_of_rank(len(frames), rank, world)
         grouped = (not ctx.scaled and not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "test_group") and model.takes_groups())
@@ -392,7 +413,7 @@ def _test(ctx, timing):
                 tmax = torch.tensor([dt], dtype=torch.float64, device=device)
                 dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
                 dt = float(tmax.item())
-            per_frame = 3 * frames.height * frames.width * 3 if grouped else 0
+            per_frame = getattr(frames, "upload_bytes_per_frame", 3 * frames.height * frames.width * 3) if grouped else 0
             timing.update({"seconds": dt, "frames": len(frames), "frames_local": len(mine), "h2d_bytes": per_frame * len(mine),
                            "grouped": grouped, "frames_per_call": frames.group if grouped else 1})
         tables.append(table)
@@ -435,7 +456,7 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
     import torch.distributed as dist
     from utils import sharding as sh
     from utils.data import prefetch_groups
-    from utils.writer import FrameWriter, truncate_raw
+    from utils.writer import FrameWriter, truncate_raw, truncate_y4m, y4m_options
     rank, world, on_cpu, device, model, loaders, fence = ctx.rank, ctx.world, ctx.on_cpu, ctx.device, ctx.model, ctx.loaders, ctx.fence
     depth, workers = int(writer_cfg.get("depth", 3)), int(writer_cfg.get("workers", 4))
     if not on_cpu:
@@ -447,10 +468,25 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
         mine = sh.frames_of_rank(len(frames), rank, world)
         grouped = (not views and not ctx.scaled and not on_cpu and hasattr(frames, "host_chunk") and hasattr(model, "predict_group")
                    and model.takes_groups())
+        y4m = None
+        if fmt == "y4m":
+            # with a Y4M input the stream's rate, aspect, siting and range are its own; the command line's rate / aspect win
+            if not hasattr(frames, "height") or not hasattr(frames, "width"):
+                raise SystemExit("--format y4m needs a loader of ONE frame size (a video); %s has none" % type(frames).__name__)
+            head = getattr(frames, "header", None)
+            y4m = {"fps": writer_cfg.get("y4m_fps") or (head.fps if head is not None and head.fps != "0:0" else None),
+                   "aspect": writer_cfg.get("y4m_aspect") or (head.aspect if head is not None and head.aspect != "0:0" else None),
+                   "matrix": getattr(frames, "matrix", None), "range": getattr(frames, "range", None), "siting": getattr(frames, "siting", None)}
+            try:
+                y4m_options(y4m)                            # every rank refuses a bad ratio, before any of them waits for another
+            except ValueError as e:
+                raise SystemExit("--format y4m: %s" % e)
         if rank == 0:
             os.makedirs(out_dir, exist_ok=True)
             if fmt == "raw":
                 truncate_raw(out_dir)                       # once, before any rank opens the file
+            elif fmt == "y4m":
+                truncate_y4m(out_dir, frames.height, frames.width, y4m)
         fence()
         # device uint8 ring, one slot per writer slot: a slot is packed into again only after its download has completed (the
         # stream waits for the event, the host does not)
@@ -507,7 +543,7 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
                     downloaded[slot] = writer.submit([f], u8)
 
         writer = FrameWriter(out_dir, fmt, depth=depth, workers=workers, n_frames=len(frames), device=None if on_cpu else device,
-                             png_encoder=writer_cfg.get("png_encoder", "host"))
+                             png_encoder=writer_cfg.get("png_encoder", "host"), y4m=y4m)
         with writer:
             if timing is not None and li == 0:
                 if grouped:
@@ -526,8 +562,13 @@ def _predict(ctx, output, fmt, writer_cfg, timing, views=None):
                 dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
                 dt = float(tmax.item())
             per_frame = frames.height * frames.width * 3 if grouped else 0
-            timing.update({"seconds": dt, "frames": len(frames), "frames_local": len(mine), "h2d_bytes": 3 * per_frame * len(mine),
-                           "d2h_bytes": per_frame * len(mine), "grouped": grouped, "frames_per_call": frames.group if grouped else 1})
+            up = getattr(frames, "upload_bytes_per_frame", 3 * per_frame) if grouped else 0
+            if fmt == "y4m" and grouped:
+                down = frames.height * frames.width + 2 * ((frames.height + 1) // 2) * ((frames.width + 1) // 2)
+            else:
+                down = per_frame
+            timing.update({"seconds": dt, "frames": len(frames), "frames_local": len(mine), "h2d_bytes": up * len(mine),
+                           "d2h_bytes": down * len(mine), "grouped": grouped, "frames_per_call": frames.group if grouped else 1})
         written += len(frames)
         if rank == 0:
             suffix = "/dataloader_idx_%d" % li if len(loaders) > 1 else ""

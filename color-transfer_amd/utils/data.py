@@ -18,6 +18,9 @@
   streams in ONE call (a stream occupies one wave: a call needs many to fill the GPU).
 * `prefetch(dataset, indices, device)` -- yields device-resident samples while the next one is decoded into PINNED host
   memory and uploaded on a second stream (double buffer), so that the transfer kernels never wait for PCIe.
+* `StereoY4MVideo(target, reference, gt=None)` / `SyntheticStereoVideoYUV` -- stereo video as 8-bit Y'CbCr 4:2:0: Y4M files (utils/y4m.py,
+  the stand-in for the reference's cv2.VideoCapture) or synthetic I420 chunks.  `prefetch_groups` uploads the YUV bytes (1.5 per pixel
+  instead of 3) and decodes a whole chunk with ONE ct_hip.yuv420_to_rgb launch into the [3,k,H,W,3] RGB groups every grouped method takes.
 Seeds are derived from the FRAME index (world-size independent)."""
 import os
 from pathlib import Path
@@ -500,12 +503,218 @@ class SyntheticStereoVideoU8:
         return {k: (c[i].permute(2, 0, 1).float() / 255) for i, k in enumerate(self.roles)}
 
 
+YUV_ROLES = ("target", "reference", "gt")
+
+
+class _YuvGroups:
+    """what the two YUV datasets share: the geometry, the decode of an uploaded chunk and the per-frame sample"""
+
+    def _init_yuv(self, height, width, group, matrix, range_, siting, n_roles):
+        import ct_hip
+        if matrix not in ct_hip.YUV_MATRICES or range_ not in ct_hip.YUV_RANGES or siting not in ct_hip.YUV_SITINGS:
+            raise ValueError("yuv_matrix %r / yuv_range %r / siting %r: one of %s / %s / %s"
+                             % (matrix, range_, siting, sorted(ct_hip.YUV_MATRICES), sorted(ct_hip.YUV_RANGES), sorted(ct_hip.YUV_SITINGS)))
+        if int(group) < 1:
+            raise ValueError("group must be >= 1 (got %r)" % (group,))
+        self.height, self.width, self.group = int(height), int(width), int(group)
+        self.matrix, self.range, self.siting = matrix, range_, siting
+        self.frame_bytes = ct_hip.yuv420_frame_bytes(self.height, self.width)
+        self.roles = YUV_ROLES[:n_roles]
+        self.has_gt = n_roles == 3
+        self.upload_bytes_per_frame = n_roles * self.frame_bytes        # what one frame of every role costs on the host link
+
+    def decode_group(self, dev, k, out):
+        """dev: the uploaded chunk, device uint8 [roles][group][frame_bytes], its first k frames per role valid; out: device uint8
+        [roles][group][H][W][3].  A full chunk is ONE ct_hip.yuv420_to_rgb launch over roles * group frames, a ragged one a launch
+        per role.  Returns out[:, :k]."""
+        import ct_hip
+        roles, g = dev.shape[0], dev.shape[1]
+        kw = dict(matrix=self.matrix, range=self.range, siting=self.siting)
+        if k == g:
+            ct_hip.yuv420_to_rgb(dev.view(roles * g, self.frame_bytes), self.height, self.width, out=out.view(roles * g, self.height, self.width, 3), **kw)
+        else:
+            for r in range(roles):
+                ct_hip.yuv420_to_rgb(dev[r, :k], self.height, self.width, out=out[r, :k], **kw)
+        return out[:, :k]
+
+    def __getitem__(self, f):
+        """one frame as the reference's sample dict (float32 CHW in [0,1], on the device): float32(byte) / 255 of the same
+        kernel's bytes.  Without a gt stream the gt role is the target's frame."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("%s decodes on the GPU (ct_hip.yuv420_to_rgb): there is no CPU path" % type(self).__name__)
+        f = int(f)
+        if not 0 <= f < len(self):
+            raise IndexError(f)
+        device = torch.device("cuda", torch.cuda.current_device())
+        dev = self.stage_chunk([f], None)[:, :1].to(device).contiguous()       # a blocking copy: the pinned buffer is reused by the next call
+        rgb = torch.empty((dev.shape[0], 1, self.height, self.width, 3), dtype=torch.uint8, device=device)
+        self.decode_group(dev, 1, rgb)
+        # float32(byte) / 255 correctly rounded, from a host-made table (a device division need not round like the host's)
+        table = (torch.arange(256, dtype=torch.float32) / 255).to(device)
+        chw = table[rgb[:, 0].permute(0, 3, 1, 2).long()]
+        sample = {k: chw[i] for i, k in enumerate(self.roles)}
+        sample.setdefault("gt", sample["target"])
+        return sample
+
+
+class StereoY4MVideo(_YuvGroups):
+    """Stereo video from Y4M files (utils/y4m.py): the distorted view `target`, the other view `reference` and, for `test`, the
+    ground truth `gt`, 8-bit 4:2:0 progressive, of one size, siting and range; the length is the shortest file's.  Frames travel
+    as YUV: `stage_chunk` preads the frames of a group straight into a pinned [roles][group][frame_bytes] buffer, `prefetch_groups`
+    uploads it and `decode_group` makes the RGB group on the device.  range: None follows the files' XCOLORRANGE, else "limited".
+    Without gt, `predict` works (two roles are uploaded) and `test` is refused."""
+
+    def __init__(self, target, reference, gt=None, group=8, matrix="bt709", range=None):
+        from utils import y4m
+        paths = [os.fspath(p) for p in (target, reference) + ((gt,) if gt else ())]
+        parsed = [y4m.frame_offsets(p) for p in paths]
+        heads = [h for h, _ in parsed]
+        for p, h in zip(paths[1:], heads[1:]):
+            if (h.width, h.height) != (heads[0].width, heads[0].height):
+                raise ValueError("%s is %d x %d, %s is %d x %d: the streams must agree in size"
+                                 % (paths[0], heads[0].width, heads[0].height, p, h.width, h.height))
+            if h.siting != heads[0].siting or h.color_range != heads[0].color_range:
+                raise ValueError("%s and %s differ in chroma siting or XCOLORRANGE: one decode serves a whole group" % (paths[0], p))
+        self.header = heads[0]
+        self.paths = paths
+        self._offsets = [o for _, o in parsed]
+        self.n_frames = min(len(o) for o in self._offsets)
+        self._init_yuv(heads[0].height, heads[0].width, group, matrix, range or heads[0].color_range or "limited", heads[0].siting,
+                       len(paths))
+        self._fds = [os.open(p, os.O_RDONLY) for p in paths]
+        self._pinned = {}
+
+    def __len__(self):
+        return self.n_frames
+
+    def close(self):
+        for fd in self._fds:
+            os.close(fd)
+        self._fds = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stage_chunk(self, ids, slot):
+        """the frames `ids` (at most `group`) of every role, read into the pinned buffer of `slot` ([roles][group][frame_bytes];
+        the caller keeps a slot's previous upload from being overwritten) and returned"""
+        buf = self._pinned.get(slot)
+        if buf is None:
+            buf = torch.empty((len(self.roles), self.group, self.frame_bytes), dtype=torch.uint8)
+            buf = self._pinned[slot] = buf.pin_memory() if torch.cuda.is_available() else buf
+        arr = buf.numpy()
+        for r, (fd, offsets) in enumerate(zip(self._fds, self._offsets)):
+            for j, f in enumerate(ids):
+                view, done = memoryview(arr[r, j]), 0
+                while done < self.frame_bytes:
+                    got = os.preadv(fd, [view[done:]], offsets[f] + done)
+                    if got <= 0:
+                        raise IOError("%s: frame %d ends early" % (self.paths[r], f))
+                    done += got
+        return buf
+
+    def host_chunk(self, first_frame):
+        """the pinned chunk of the `group` consecutive frames from `first_frame` (fewer at the end of the video), as YUV bytes"""
+        first_frame = int(first_frame)
+        return self.stage_chunk(range(first_frame, min(first_frame + self.group, self.n_frames)), "host_chunk")
+
+
+class SyntheticStereoVideoYUV(_YuvGroups):
+    """`--data.synthetic video_yuv`: SyntheticStereoVideoU8's pinned-pool scheme with packed I420 chunks,
+    [3 roles][group][frame_bytes] of random bytes: the same frames-per-second question at 1.5 bytes per pixel on the link, with no
+    disk in the measurement."""
+
+    def __init__(self, n_frames=1000, height=1080, width=1920, group=8, pool=8, matrix="bt709", range="limited", siting="center"):
+        self.n_frames, self.pool = int(n_frames), int(pool)
+        self._init_yuv(height, width, group, matrix, range or "limited", siting, 3)
+        self._chunks = None
+
+    def __len__(self):
+        return self.n_frames
+
+    def _chunk(self, i):
+        if self._chunks is None:
+            self._chunks = [None] * self.pool
+        if self._chunks[i] is None:
+            rng = np.random.default_rng(8765 + i)
+            t = torch.from_numpy(rng.integers(0, 256, (3, self.group, self.frame_bytes), dtype=np.uint8))
+            self._chunks[i] = t.pin_memory() if torch.cuda.is_available() else t
+        return self._chunks[i]
+
+    _pool_index = SyntheticStereoVideoU8._pool_index
+
+    def prepare(self, indices):
+        idx = list(indices)
+        for c in range(0, len(idx), self.group):
+            self._chunk(self._pool_index(idx[c]))
+
+    def host_chunk(self, first_frame):
+        """as SyntheticStereoVideoU8.host_chunk: a group's content is defined by its first frame"""
+        return self._chunk(self._pool_index(first_frame))
+
+    def stage_chunk(self, ids, slot):
+        return self.host_chunk(list(ids)[0])
+
+
+def _prefetch_yuv_groups(dataset, indices, device, depth=3):
+    """prefetch_groups for a dataset of YUV chunks (`stage_chunk`, `decode_group`): the same copy stream and ring of `depth` device
+    buffers, of [roles][group][frame_bytes] YUV bytes; after a chunk's upload event the consumer's stream runs the dataset's decode
+    (one launch for a full chunk) into a ring of RGB buffers of its own and the [roles,k,H,W,3] RGB group is yielded.  The YUV
+    buffer is free again once that decode has run, the RGB buffer when the consumer's stream reaches its next use."""
+    indices = list(indices)
+    g = dataset.group
+    n_chunks = (len(indices) + g - 1) // g
+    if n_chunks == 0:
+        return
+    copy_stream = torch.cuda.Stream(device=device)
+    main = torch.cuda.current_stream(device)
+    roles, fb = len(dataset.roles), dataset.frame_bytes
+    ring = [torch.empty((roles, g, fb), dtype=torch.uint8, device=device) for _ in range(depth)]
+    rgb = [torch.empty((roles, g, dataset.height, dataset.width, 3), dtype=torch.uint8, device=device) for _ in range(depth)]
+    uploaded = [torch.cuda.Event() for _ in range(depth)]
+    consumed = [torch.cuda.Event() for _ in range(depth)]
+
+    def ids_of(c):
+        return indices[c * g:c * g + g]
+
+    def upload(c):
+        slot, ids = c % depth, ids_of(c)
+        if c >= depth:
+            uploaded[slot].synchronize()            # host: the pinned buffer of this slot is the source of that earlier copy
+        src = dataset.stage_chunk(ids, slot)
+        with torch.cuda.stream(copy_stream):
+            if c >= depth:
+                copy_stream.wait_event(consumed[slot])
+            if len(ids) == g:
+                ring[slot].copy_(src, non_blocking=True)
+            else:
+                ring[slot][:, :len(ids)].copy_(src[:, :len(ids)], non_blocking=True)
+            uploaded[slot].record(copy_stream)
+
+    for c in range(min(depth - 1, n_chunks)):
+        upload(c)
+    for c in range(n_chunks):
+        if c + depth - 1 < n_chunks:
+            upload(c + depth - 1)
+        slot, ids = c % depth, ids_of(c)
+        main.wait_event(uploaded[slot])
+        frames = dataset.decode_group(ring[slot], len(ids), rgb[slot])
+        consumed[slot].record(main)
+        yield ids, frames
+
+
 def prefetch_groups(dataset, indices, device, depth=3):
     """Yield (frame indices of the group, device uint8 tensor [3, k, H, W, 3]) for a dataset with `host_chunk` (pinned uint8 chunks
     of `dataset.group` frames): the uploads run on a copy stream, depth - 1 uploads ahead of the consumer, through a ring of
     `depth` device buffers; a buffer is overwritten only after the kernels that read its previous chunk are done (the consumer's
     stream is the current one when the generator is advanced).  Copy size is what the PCIe rate hangs on (measured round 5,
     1080p triples, same box): one triple per copy 47.8 GB/s, four (75 MB) 49-52, eight (149 MB, the default group) 56."""
+    if hasattr(dataset, "decode_group"):            # YUV chunks (StereoY4MVideo, SyntheticStereoVideoYUV): decoded on the device
+        yield from _prefetch_yuv_groups(dataset, indices, device, depth)
+        return
     indices = list(indices)
     g = dataset.group
     n_chunks = (len(indices) + g - 1) // g
@@ -548,7 +757,10 @@ class DataModule:
     """Accepts the reference's init_args (data_dir, num_workers, crop_size, ...).  `test_frames()` = the reference's first test
     loader (ArtificialTestDataset over data_dir / "Test") when that directory exists; otherwise a synthetic stand-in:
     `synthetic: video` (default, n_frames float frames), `synthetic: artificial` (n_frames uint8 pairs x 31 distortions) or
-    `synthetic: video_u8` (n_frames uint8 frames in pinned groups of `group` = 8: configs[4]).
+    `synthetic: video_u8` (n_frames uint8 frames in pinned groups of `group` = 8: configs[4]) or `synthetic: video_yuv` (the same as
+    packed I420 chunks, decoded on the device).  `y4m_target` (+ `y4m_reference`, optional `y4m_gt`): the dataset is StereoY4MVideo
+    over those Y4M files, whatever else is given; `yuv_matrix` ("bt709") and `yuv_range` (None: the files' XCOLORRANGE, else limited)
+    choose the conversion.
     `val_dataloader()` = the reference's two validation loaders (utils/data.py:150-166): ArtificialTrainValDataset over data_dir /
     "Validation" in batches of `batch_size`, and the real-world set one frame per batch; without those directories `synthetic:
     trainval` stands in (n_frames uint8 pairs x image_repeats crops; n_frames float frames for the real-world loader).  `crop_size`,
@@ -557,17 +769,24 @@ class DataModule:
     the datasets that read files; the synthetic ones have nothing to decode."""
 
     def __init__(self, data_dir=None, num_workers=0, crop_size=None, image_repeats=None, batch_size=None,
-                 n_frames=8, height=270, width=480, synthetic="video", group=8, png_decoder="host", decode_ahead=16, **_):
+                 n_frames=8, height=270, width=480, synthetic="video", group=8, png_decoder="host", decode_ahead=16,
+                 y4m_target=None, y4m_reference=None, y4m_gt=None, yuv_matrix="bt709", yuv_range=None, **_):
         self.png_decoder, self.decode_ahead = check_png_decoder(png_decoder), max(int(decode_ahead), 1)
         self.data_dir = Path(data_dir) if data_dir else None
         self.crop_size, self.image_repeats, self.batch_size = crop_size, image_repeats, batch_size
         self._synthetic = (synthetic, n_frames, height, width)
-        if self.data_dir is not None and (self.data_dir / "Test").is_dir():
+        if y4m_target:
+            if not y4m_reference:
+                raise ValueError("data.y4m_target needs data.y4m_reference (the other view)")
+            self.dataset = StereoY4MVideo(y4m_target, y4m_reference, y4m_gt, group=group, matrix=yuv_matrix, range=yuv_range)
+        elif self.data_dir is not None and (self.data_dir / "Test").is_dir():
             self.dataset = ArtificialTestDataset(self.data_dir / "Test", self.png_decoder)
         elif synthetic == "artificial":
             self.dataset = SyntheticArtificialTest(n_frames, height, width)
         elif synthetic == "video_u8":
             self.dataset = SyntheticStereoVideoU8(n_frames, height, width, group=group)
+        elif synthetic == "video_yuv":
+            self.dataset = SyntheticStereoVideoYUV(n_frames, height, width, group=group, matrix=yuv_matrix, range=yuv_range)
         else:
             self.dataset = SyntheticStereoFrames(n_frames, height, width)
 

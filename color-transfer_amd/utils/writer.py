@@ -24,6 +24,13 @@ same pixels as the host encoder's; they are larger (no LZ77 matching).  HOST ten
 path under `"device"` too.  Back-pressure, errors, suffixes and the returned event are those of the host encoder; the other formats
 ignore the option.
 
+`fmt="y4m"` (with `n_frames` and `y4m=dict(fps=, aspect=, matrix=, range=, siting=)`): ONE file `frames.y4m`, 8-bit 4:2:0, that an
+encoder takes directly.  `submit` of DEVICE frames runs `ct_hip.rgb_to_yuv420` on the caller's stream into a device buffer of the slot,
+the slot's one asynchronous copy downloads the [k, frame_bytes] planes (1.5 bytes per pixel instead of 3) and the workers `pwrite`
+`FRAME\n` + planes at header_len + f * (6 + frame_bytes).  `truncate_y4m` writes the header once per run, as `truncate_raw` does for
+the raw file; sharded ranks write only their own frames and `close()` sets the full length.  Suffixed frames and host tensors are
+refused.
+
 The first error of a worker (unwritable directory, full disk) is kept and raised from the next `submit` or from `close()`."""
 import os
 import queue
@@ -32,10 +39,14 @@ import threading
 import numpy as np
 import torch
 
-FORMATS = ("png", "npy", "raw", "null")
+FORMATS = ("png", "npy", "raw", "y4m", "null")
 PNG_ENCODERS = ("host", "device")
 MAX_WORKERS = 16
 RAW_NAME = "frames.rgb"
+Y4M_NAME = "frames.y4m"
+Y4M_KEYS = ("fps", "aspect", "matrix", "range", "siting")
+Y4M_DEFAULTS = {"fps": "25:1", "aspect": "1:1", "matrix": "bt709", "range": "limited", "siting": "center"}
+Y4M_CHOICES = {"matrix": ("bt601", "bt709"), "range": ("limited", "full"), "siting": ("center", "left")}
 
 
 def frame_name(index, fmt, suffix=None):
@@ -48,6 +59,39 @@ def truncate_raw(out_dir):
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, RAW_NAME), "wb"):
         pass
+
+
+def y4m_options(y4m=None):
+    """the `y4m` argument of FrameWriter / truncate_y4m -> the complete dict; unknown keys and values raise ValueError"""
+    opts = dict(Y4M_DEFAULTS)
+    for k, v in (y4m or {}).items():
+        if k not in Y4M_KEYS:
+            raise ValueError("y4m option %r: one of %s" % (k, ", ".join(Y4M_KEYS)))
+        if v is not None:
+            opts[k] = v
+    for k, choices in Y4M_CHOICES.items():
+        if opts[k] not in choices:
+            raise ValueError("y4m %s %r: one of %s" % (k, opts[k], ", ".join(choices)))
+    from utils import y4m as container
+    container.header(2, 2, opts["fps"], opts["aspect"], opts["siting"], opts["range"])       # the ratios: refused here, not in a worker
+    return opts
+
+
+def y4m_header(height, width, y4m=None):
+    from utils import y4m as container
+    o = y4m_options(y4m)
+    return container.header(int(width), int(height), o["fps"], o["aspect"], o["siting"], o["range"])
+
+
+def truncate_y4m(out_dir, height, width, y4m=None):
+    """Create `out_dir`/frames.y4m holding the stream header alone; returns the header's length.  ONE process of a sharded run does
+    this before the others open the file (and before a barrier): the writers never truncate or write the header, they only write
+    their frames' ranges."""
+    os.makedirs(out_dir, exist_ok=True)
+    head = y4m_header(height, width, y4m)
+    with open(os.path.join(out_dir, Y4M_NAME), "wb") as fh:
+        fh.write(head)
+    return len(head)
 
 
 class _EncodedFrame:
@@ -91,11 +135,12 @@ class _Slot:
 
 
 class FrameWriter:
-    def __init__(self, out_dir, fmt="png", depth=3, workers=4, n_frames=None, device=None, png_encoder="host"):
+    def __init__(self, out_dir, fmt="png", depth=3, workers=4, n_frames=None, device=None, png_encoder="host", y4m=None):
         """workers: an explicit small number (capped at 16), never derived from the machine's CPU count.  n_frames: the length of
         the video, required for `raw` (the size of the file).  device: the GPU whose frames are submitted (default: the frames').
         png_encoder: "host" (PIL on the workers) or "device" (ct_hip.png_deflate; device tensors only, host tensors keep the PIL
-        path); only `png` looks at it."""
+        path); only `png` looks at it.  y4m: the stream's fps / aspect ("num:den") and the conversion's matrix / range / siting;
+        only `y4m` takes it."""
         if fmt not in FORMATS:
             raise ValueError("format %r: one of %s" % (fmt, ", ".join(FORMATS)))
         if png_encoder not in PNG_ENCODERS:
@@ -104,6 +149,11 @@ class FrameWriter:
             raise ValueError("depth and workers must be >= 1 (got %r, %r)" % (depth, workers))
         if fmt == "raw" and n_frames is None:
             raise ValueError("format raw needs n_frames (frame f lives at offset f*H*W*3 of one file)")
+        if fmt == "y4m" and n_frames is None:
+            raise ValueError("format y4m needs n_frames (frame f lives at header_len + f * (6 + frame_bytes) of one file)")
+        if y4m is not None and fmt != "y4m":
+            raise ValueError("the y4m options go with format y4m only (got format %r)" % fmt)
+        self.y4m = y4m_options(y4m) if fmt == "y4m" else None
         self.out_dir, self.fmt, self.png_encoder = os.fspath(out_dir), fmt, png_encoder
         self.n_frames = None if n_frames is None else int(n_frames)
         self.device = None if device is None else torch.device(device)
@@ -140,14 +190,16 @@ class FrameWriter:
         if suffix is not None:
             if not isinstance(suffix, str) or not suffix or any(ch in suffix for ch in "/\\.") or suffix != suffix.strip():
                 raise ValueError("suffix %r: a plain name without dots or path separators" % (suffix,))
-            if self.fmt == "raw":
-                raise ValueError("a raw video is one file: it takes no suffixed frames (suffix %r)" % (suffix,))
-        if self.fmt == "raw":
+            if self.fmt in ("raw", "y4m"):
+                raise ValueError("a %s video is one file: it takes no suffixed frames (suffix %r)" % (self.fmt, suffix))
+        if self.fmt == "y4m" and not frames_u8.is_cuda:
+            raise ValueError("format y4m converts on the device (ct_hip.rgb_to_yuv420): it takes device frames, not host tensors")
+        if self.fmt in ("raw", "y4m"):
             shape = tuple(frames_u8.shape[1:])
             if self._frame_shape is None:
                 self._frame_shape = shape
             elif shape != self._frame_shape:
-                raise ValueError("raw video: frames of %s after frames of %s" % (shape, self._frame_shape))
+                raise ValueError("%s video: frames of %s after frames of %s" % (self.fmt, shape, self._frame_shape))
         if not indices:
             return None
         slot = self._slots[self._next]
@@ -159,6 +211,8 @@ class FrameWriter:
         k = len(indices)
         if frames_u8.is_cuda and self.fmt == "png" and self.png_encoder == "device":
             self._submit_encoded(slot, frames_u8)
+        elif self.fmt == "y4m":
+            self._submit_y4m(slot, frames_u8)
         elif frames_u8.is_cuda:
             dev = frames_u8.device
             if slot.buf is None or slot.buf.shape[1:] != frames_u8.shape[1:] or slot.buf.shape[0] < k:
@@ -206,6 +260,29 @@ class FrameWriter:
         host_sizes, host_adler, host_streams = _encoded_views(slot.enc, k, chunks, cap)
         slot.frames = _EncodedGroup(h, w, ct_hip.PNG_ROWS_PER_CHUNK, host_sizes, host_adler, host_streams)
 
+    def _submit_y4m(self, slot, frames_u8):
+        """the YUV file: one rgb_to_yuv420 launch for the group on the caller's stream, then the slot's one copy of [k, frame_bytes]"""
+        import ct_hip
+        dev = frames_u8.device
+        k, h, w, _ = frames_u8.shape
+        fb = ct_hip.yuv420_frame_bytes(h, w)
+        if slot.dev is None or slot.dev.numel() < k * fb or slot.dev.device != dev:
+            slot.dev = torch.empty(k * fb, dtype=torch.uint8, device=dev)      # the old one is idle: the slot has nothing pending
+            slot.enc = torch.empty(k * fb, dtype=torch.uint8, pin_memory=True)
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device if self.device is not None else dev)
+        planes = slot.dev[:k * fb].view(k, fb)
+        ct_hip.rgb_to_yuv420(frames_u8.contiguous(), matrix=self.y4m["matrix"], range=self.y4m["range"], siting=self.y4m["siting"], out=planes)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(dev))
+        self._copy_stream.wait_event(ready)
+        slot.frames = slot.enc[:k * fb].view(k, fb)
+        with torch.cuda.stream(self._copy_stream):
+            slot.frames.copy_(planes, non_blocking=True)
+            slot.event = torch.cuda.Event()
+            slot.event.record(self._copy_stream)
+        frames_u8.record_stream(self._copy_stream)
+
     def close(self):
         """Drain the queue, join the workers, close the raw file, raise the first writer error.  Safe to call twice."""
         if not self._closed:
@@ -218,13 +295,20 @@ class FrameWriter:
                 try:
                     if not self._failed and self._frame_shape is not None:
                         # every rank sets the same full size: frames nobody wrote read as zeros, a longer stale file is cut
-                        os.ftruncate(self._raw_fd, self.n_frames * int(np.prod(self._frame_shape)))
+                        os.ftruncate(self._raw_fd, self._file_bytes())
                 except OSError as e:
                     self._failed, self._error = True, e
                 finally:
                     os.close(self._raw_fd)
                     self._raw_fd = None
         self._raise_pending()
+
+    def _file_bytes(self):
+        """the full length of the one file of `raw` / `y4m`"""
+        if self.fmt == "raw":
+            return self.n_frames * int(np.prod(self._frame_shape))
+        h, w = self._frame_shape[:2]
+        return len(y4m_header(h, w, self.y4m)) + self.n_frames * (6 + h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2))
 
     def __enter__(self):
         return self
@@ -290,8 +374,17 @@ class FrameWriter:
         else:
             with self._cond:
                 if self._raw_fd is None:
-                    self._raw_fd = os.open(os.path.join(self.out_dir, RAW_NAME), os.O_WRONLY | os.O_CREAT, 0o666)
+                    self._raw_fd = os.open(os.path.join(self.out_dir, Y4M_NAME if self.fmt == "y4m" else RAW_NAME), os.O_WRONLY | os.O_CREAT, 0o666)
             data = memoryview(np.ascontiguousarray(arr)).cast("B")
-            offset, done = index * len(data), 0
+            if self.fmt == "y4m":                           # `arr`: the frame's planes; its FRAME line goes in front of them
+                h, w = self._frame_shape[:2]
+                offset = len(y4m_header(h, w, self.y4m)) + index * (6 + len(data))
+                done = 0
+                while done < 6:
+                    done += os.pwrite(self._raw_fd, b"FRAME\n"[done:], offset + done)
+                offset += 6
+            else:
+                offset = index * len(data)
+            done = 0
             while done < len(data):
                 done += os.pwrite(self._raw_fd, data[done:], offset + done)

@@ -950,6 +950,35 @@ int ct_warp_perspective_u8(const uint8_t *raw, int n, int src_h, int src_w, int 
                            int crop_h, const double *maps, int shared, int out_x, int out_y, int out_w, int out_h, uint8_t *out,
                            int path, void *stream);
 
+/* ---- 8-bit Y'CbCr 4:2:0 <-> RGB bytes (csrc/yuv.hip, csrc/ct_yuv.h): what cv2.VideoCapture + swscale do
+ * on the host in the reference (utils/postprocess.py:78-103), here on the device so that the link carries 1.5 bytes per pixel.
+ * A frame is a packed I420 buffer: the Y plane [height][width], then Cb and Cr [ch][cw], ch = ceil(height / 2), cw = ceil(width / 2);
+ * frame f starts at yuv + f * frame_stride bytes, frame_stride >= height * width + 2 * ch * cw.  RGB is uint8 [n][height][width][3].
+ * Both directions give the correctly rounded value, ties to even, of an exact rational expression, computed in integers:
+ *   Kr, Kb: BT.601 299/1000, 114/1000; BT.709 2126/10000, 722/10000; Kg = 1 - Kr - Kb
+ *   (Yoff, Ys, Cs): limited (16, 219, 224), encode clamps Y to 16..235 and C to 16..240; full (0, 255, 255); chroma offset 128
+ *   siting: centre = chroma at luma (2i + 1/2, 2j + 1/2) (Y4M C420jpeg / C420); left = at (2i + 1/2, 2j) (C420mpeg2)
+ *   decode: chroma at a luma position is the bilinear interpolation of the plane (indices clamped), an exact count of sixteenths
+ *     C16; y' = (Y - Yoff) / Ys, c' = (C16 - 2048) / (16 Cs), R' = y' + 2 (1 - Kr) cr', B' = y' + 2 (1 - Kb) cb',
+ *     G' = y' - (2 Kb (1 - Kb) / Kg) cb' - (2 Kr (1 - Kr) / Kg) cr';  byte = rint(255 clamp(., 0, 1)).  Every input byte is taken.
+ *   encode: Y = clamp(rint(Yoff + Ys (Kr r + Kg g + Kb b) / 255)); chroma from the exact weighted mean over the footprint (centre:
+ *     the 2x2 box; left: (1, 2, 1) / 4 on columns 2j - 1 .. 2j + 1, two rows averaged; luma indices clamped to the frame):
+ *     Cb = clamp(rint(128 + Cs (b - y) / (255 * 2 (1 - Kb)))), Cr likewise with r and Kr.
+ * swscale / cv2 parity is unpinned (neither is present offline).  Any alignment and odd sizes are taken: runs of 16 luma columns
+ * whose addresses sit on the 16-byte grid move as vectors, the rest byte by byte.  No workspace, deterministic.
+ * CT_E_BADARG, before anything is launched: a null pointer, n, height or width < 1, height * width * 3 >= 2^31, a stride smaller
+ * than the frame, n * ch * ceil(width / 16) >= 2^31 - 2^21, an unknown matrix, range or siting.  Added under ABI 9.             */
+#define CT_YUV_BT601 0
+#define CT_YUV_BT709 1
+#define CT_YUV_LIMITED 0
+#define CT_YUV_FULL 1
+#define CT_YUV_SITING_CENTER 0
+#define CT_YUV_SITING_LEFT 1
+int ct_yuv420_to_rgb_u8(const uint8_t *yuv, int64_t frame_stride, int n, int height, int width, int matrix, int range, int siting,
+                        uint8_t *out_rgb, void *stream);
+int ct_rgb_to_yuv420_u8(const uint8_t *rgb, int n, int height, int width, int matrix, int range, int siting, uint8_t *out_yuv,
+                        int64_t frame_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
